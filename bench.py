@@ -9,8 +9,16 @@ tables, WGL search for every key, verdict summary, then (N > 1) the RCCL
 all-reduce of the verdict summary across ranks. Each rank checks its own
 10k-key shard (keys are independent: weak scaling, no data-path collective).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the result line.
+--full adds everything else the line can carry: the host-buffer (PCIe-
+inclusive) rate, the key-by-key parity of the timed verdicts with the CPU
+oracle, the two CPU baselines and the recorded PMC traffic of the dominant
+kernel (--no-cpu, --no-parity and --e2e 0 drop single parts of it).
+--dump-outputs DIR writes what the last timed step returned (the per-key
+verdicts and the verdict summary) as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -177,9 +185,18 @@ def parse():
     ap.add_argument("--ops-per-key", type=int, default=500)
     ap.add_argument("--cpu-sample-keys", type=int, default=None,
                     help="keys of the rank-0 history timed on the CPU (default per workload)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--e2e", type=int, default=1, help="also time one call from host buffers (PCIe-inclusive)")
-    ap.add_argument("--no-parity", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline value does not need: the host-buffer "
+                         "rate (--e2e), parity with the CPU oracle, the CPU baselines, the recorded PMC "
+                         "traffic of the dominant kernel")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one returned -- every field of the "
+                         "per-key verdicts and the deterministic fields of the verdict summary -- as "
+                         "DIR/<name>.npy (float64; every value is an integer below 2^53)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: no CPU baselines")
+    ap.add_argument("--e2e", type=int, default=1,
+                    help="with --full: also time one call from host buffers (PCIe-inclusive)")
+    ap.add_argument("--no-parity", action="store_true", help="with --full: no parity check")
     ap.add_argument("--seed-rank", type=int, default=None,
                     help="generate the history rank R of a multi-GPU run would check (rehearsal on one GPU)")
     ap.add_argument("--pool", type=int, default=0,
@@ -197,6 +214,8 @@ def parse():
     a = ap.parse_args()
     a.tune = {k: int(v) for k, v in (o.split("=", 1) for o in a.opt)}
     a.shard_rn = tuple(int(x) for x in a.shard.split("/")) if a.shard else None
+    if not a.full:
+        a.no_cpu, a.no_parity, a.e2e = True, True, 0
     return a
 
 
@@ -398,7 +417,11 @@ def main():
     dom = max(phases, key=lambda k: phases[k]["ms"]) if phases else None
     seed_used = wl["seed"] + 7919 * (rank if args.seed_rank is None else args.seed_rank)
     tr, traffic_src = (pmc_traffic(args.workload, seed_used, phases[dom]["kernel"])
-                       if dom and args.keys is None else (None, None))
+                       if args.full and dom and args.keys is None else (None, None))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, s, A.VERDICT_FIELDS,
+                     pool_home["verdicts"] if use_pool else
+                     np.frombuffer(verd.cpu().numpy().tobytes(), dtype=A.VERDICT_DTYPE))
 
     # host buffers to host verdicts (H2D copy + check + verdicts D2H), over K
     # calls: the boundary's host-buffer entry point, beside the HBM-resident value
@@ -530,6 +553,30 @@ def main():
     if dist is not None:
         dist.destroy_process_group()
     return out
+
+
+# the verdict summary's fields that depend on the history and the options
+# alone (the times, probe counters and schedule counters vary from run to run)
+SUMMARY_DUMP = ("valid", "n_invalid", "n_unknown", "first_fail_entry", "n_keys")
+
+
+def dump_outputs(path, rank, s, fields, verdicts):
+    """--dump-outputs: what the last timed step handed its caller. One file
+    per jh_key_verdict field (`fields`: `verdict_<field>.npy`, one value per
+    key of this rank's shard, in key order) and `summary.npy` (SUMMARY_DUMP,
+    in that order; the all-reduced values where N > 1), all float64: the
+    values are int32 / int64 codes, row numbers and counts far below 2^53
+    (56 B per key: 0.56 MB on C3, 7 MB on a C4 shard). `explored` is
+    WGL's count where the call counted and EXPLORED_UNCOUNTED (-3) for a valid
+    key the reachable-set engine settled (exact_count=False, the timed path).
+    Ranks above 0 write `rank<r>_verdict_<field>.npy`."""
+    os.makedirs(path, exist_ok=True)
+    pre = "" if rank == 0 else f"rank{rank}_"
+    for f in fields:
+        np.save(os.path.join(path, f"{pre}verdict_{f}.npy"), verdicts[f].astype(np.float64))
+    if rank == 0:
+        np.save(os.path.join(path, "summary.npy"),
+                np.array([getattr(s, f) for f in SUMMARY_DUMP], dtype=np.float64))
 
 
 def phase_table(sums):

@@ -9,11 +9,11 @@ R=$GRAFT_REPO_ROOT
 cd $R && mkdir -p $O
 timeout -k 10 900 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread > $O/gpu_tests.log 2>&1 || exit 1
 timeout -k 10 120 python -u -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || exit 1
-timeout -k 10 400 python -u bench.py > $O/bench_c3.log 2>&1 || exit 1
-timeout -k 10 200 python -u bench.py --steps 5 --warmup 1 --no-cpu --seed-rank 3 > $O/bench_c3_rank3.log 2>&1 || exit 1
-timeout -k 10 200 python -u bench.py --steps 5 --warmup 1 --no-cpu --seed-rank 6 > $O/bench_c3_rank6.log 2>&1 || exit 1
-timeout -k 10 300 python -u bench.py --workload c4 --steps 3 --warmup 1 --no-cpu > $O/bench_c4.log 2>&1 || exit 1
-timeout -k 10 300 python -u bench.py --workload c5 --steps 1 --warmup 1 --no-cpu > $O/bench_c5.log 2>&1 || exit 1
+timeout -k 10 400 python -u bench.py --full > $O/bench_c3.log 2>&1 || exit 1
+timeout -k 10 200 python -u bench.py --full --steps 5 --warmup 1 --no-cpu --seed-rank 3 > $O/bench_c3_rank3.log 2>&1 || exit 1
+timeout -k 10 200 python -u bench.py --full --steps 5 --warmup 1 --no-cpu --seed-rank 6 > $O/bench_c3_rank6.log 2>&1 || exit 1
+timeout -k 10 300 python -u bench.py --full --workload c4 --steps 3 --warmup 1 --no-cpu > $O/bench_c4.log 2>&1 || exit 1
+timeout -k 10 300 python -u bench.py --full --workload c5 --steps 1 --warmup 1 --no-cpu > $O/bench_c5.log 2>&1 || exit 1
 timeout -k 10 300 python -u tools/bench_c2.py > $O/bench_c2.log 2>&1 || exit 1
 cd /tmp && export TMPDIR=/tmp
 timeout -s KILL 300 rocprofv3 --kernel-trace --stats -d $R/$O/ks_c3 -o c3 --output-format csv -- python3 $R/bench.py --steps 5 --warmup 1 --no-cpu --e2e 0 --no-parity > $R/$O/ks_c3.log 2>&1 || exit 1

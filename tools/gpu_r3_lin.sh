@@ -8,9 +8,9 @@ cd $R && mkdir -p $O
 T="python -u -m pytest -x -v --timeout 300 --timeout-method thread"
 timeout -k 10 400 $T tests/test_gpu_lin.py -k "bfs_exact or linear or frontier or heavy_key or c3_scale" > $O/bfs_tests.log 2>&1 || exit 1
 timeout -k 10 700 $T tests/test_gpu_lin.py tests/test_gpu_limits.py tests/test_gpu_configs.py > $O/lin_tests.log 2>&1 || exit 1
-timeout -k 10 200 python -u bench.py --steps 5 --warmup 1 --no-cpu --e2e 0 > $O/bench_c3.log 2>&1 || exit 1
-timeout -k 10 200 python -u bench.py --steps 3 --warmup 1 --no-cpu --e2e 0 --seed-rank 3 > $O/bench_c3_rank3.log 2>&1 || exit 1
-timeout -k 10 200 python -u bench.py --steps 3 --warmup 1 --no-cpu --e2e 0 --seed-rank 6 > $O/bench_c3_rank6.log 2>&1 || exit 1
+timeout -k 10 200 python -u bench.py --full --steps 5 --warmup 1 --no-cpu --e2e 0 > $O/bench_c3.log 2>&1 || exit 1
+timeout -k 10 200 python -u bench.py --full --steps 3 --warmup 1 --no-cpu --e2e 0 --seed-rank 3 > $O/bench_c3_rank3.log 2>&1 || exit 1
+timeout -k 10 200 python -u bench.py --full --steps 3 --warmup 1 --no-cpu --e2e 0 --seed-rank 6 > $O/bench_c3_rank6.log 2>&1 || exit 1
 JH_LIB=$R/jepsen_amd/variants/libjh_tune.so JH_DEBUG=2 timeout -k 10 200 python -u bench.py --steps 1 --warmup 1 --no-cpu --e2e 0 --no-parity --seed-rank 3 > $O/dbg_rank3.log 2>&1 || exit 1
 if [ "$2" = "c2" ]; then bash tools/gpu_c2.sh $O/c2 || exit 1; fi
 exit 0

@@ -41,12 +41,12 @@ tests)
 final)
   timeout -k 10 1000 python -u -m pytest -x -v --timeout 150 --timeout-method thread tests -m gpu > $O/gpu_tests.log 2>&1 || exit 1
   timeout -k 10 120 python -u -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1 || exit 1
-  timeout -k 10 300 python -u bench.py > $O/bench_c3.json 2> $O/bench_c3.err || exit 1
+  timeout -k 10 300 python -u bench.py --full > $O/bench_c3.json 2> $O/bench_c3.err || exit 1
   cd /tmp && export TMPDIR=/tmp
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/c3prof -o c3 -- python3 $R/bench.py --steps 5 --warmup 0 --no-cpu --e2e 0 --no-parity > $R/$O/c3prof.log 2>&1 ;;
 bench)
   N=$1; shift
-  timeout -k 10 600 python -u bench.py "$@" > $O/$N.json 2> $O/$N.err ;;
+  timeout -k 10 600 python -u bench.py --full "$@" > $O/$N.json 2> $O/$N.err ;;
 ranks)
   for rk in 1 2 3 4 5 6 7; do
     timeout -k 10 120 python -u bench.py --no-cpu --e2e 0 --no-parity --steps 5 --warmup 1 --seed-rank $rk "$@" > $O/c3r${rk}.json 2> $O/c3r${rk}.err || exit 1
@@ -65,15 +65,15 @@ evidence)
   for rk in 1 2 3 4 5 6 7; do
     timeout -k 10 120 python -u bench.py --no-cpu --e2e 0 --no-parity --steps 5 --warmup 1 --seed-rank $rk > $O/c3r${rk}.json 2> $O/c3r${rk}.err || exit 1
   done
-  JH_BENCH_DIST1=1 timeout -k 10 300 python -u -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --steps 5 --warmup 1 --no-cpu --e2e 0 --pool 1 > $O/dist1.json 2> $O/dist1.err || exit 1
-  JH_BENCH_DIST1=1 timeout -k 10 300 python -u -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29534 bench.py --steps 5 --warmup 1 --no-cpu --e2e 0 > $O/dist1_pool0.json 2> $O/dist1_pool0.err || exit 1
+  JH_BENCH_DIST1=1 timeout -k 10 300 python -u -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --steps 5 --warmup 1 --no-cpu --e2e 0 --pool 1 > $O/dist1.json 2> $O/dist1.err || exit 1
+  JH_BENCH_DIST1=1 timeout -k 10 300 python -u -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29534 bench.py --full --steps 5 --warmup 1 --no-cpu --e2e 0 > $O/dist1_pool0.json 2> $O/dist1_pool0.err || exit 1
   cd /tmp && export TMPDIR=/tmp
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/c2prof -o c2 -- python3 $R/tools/bench_c2.py --steps 5 --warmup 1 > $R/$O/bench_c2.log 2>&1 ;;
 evidence2)
   # part 2: C4, C5, and the C3 search kernels' FETCH_SIZE / WRITE_SIZE passes
   # (tools/pmc_traffic.py on the CPU side)
-  timeout -k 10 400 python -u bench.py --workload c4 --steps 3 --warmup 1 > $O/bench_c4.json 2> $O/bench_c4.err || exit 1
-  timeout -k 10 400 python -u bench.py --workload c5 --steps 1 --warmup 1 > $O/bench_c5.json 2> $O/bench_c5.err || exit 1
+  timeout -k 10 400 python -u bench.py --full --workload c4 --steps 3 --warmup 1 > $O/bench_c4.json 2> $O/bench_c4.err || exit 1
+  timeout -k 10 400 python -u bench.py --full --workload c5 --steps 1 --warmup 1 > $O/bench_c5.json 2> $O/bench_c5.err || exit 1
   bash tools/gpu_pmc.sh c3 'k_lin_seq_lw' $O/pmc_c3 0 && bash tools/gpu_pmc.sh c3 'k_lin_dfs' $O/pmc_c3p1 0 ;;
 ab)
   # alternating C3 runs of the in-tree build and of variants/libjh_<v>.so
@@ -143,7 +143,7 @@ pmc_v)
 c4)
   N=$1; V=$2
   L=""; [ -n "$V" ] && L=$R/jepsen_amd/variants/libjh_$V.so
-  JH_LIB=$L timeout -k 10 400 python -u bench.py --workload c4 --steps 3 --warmup 1 --no-cpu --e2e 0 > $O/c4_$N.json 2> $O/c4_$N.err ;;
+  JH_LIB=$L timeout -k 10 400 python -u bench.py --full --workload c4 --steps 3 --warmup 1 --no-cpu --e2e 0 > $O/c4_$N.json 2> $O/c4_$N.err ;;
 c2)
   timeout -k 10 200 python -u tools/bench_c2.py --steps 5 --warmup 1 --e2e > $O/$1.log 2>&1 ;;
 abenv)
@@ -206,12 +206,12 @@ ev6a)
   for rk in 1 2 3 4 5 6 7; do
     timeout -k 10 120 python -u bench.py --no-cpu --e2e 0 --no-parity --steps 5 --warmup 1 --seed-rank $rk > $O/c3r${rk}.json 2> $O/c3r${rk}.err || exit 1
   done
-  timeout -k 10 300 python -u bench.py --no-cpu --e2e 0 --steps 10 --warmup 2 --budget 1048576 --opt flags=1024 > $O/c3_r4def.json 2> $O/c3_r4def.err ;;
+  timeout -k 10 300 python -u bench.py --full --no-cpu --e2e 0 --steps 10 --warmup 2 --budget 1048576 --opt flags=1024 > $O/c3_r4def.json 2> $O/c3_r4def.err ;;
 ev6b)
   # part b: C4, C5, C2 under a kernel trace, the one-rank RCCL path
-  timeout -k 10 400 python -u bench.py --workload c4 --steps 3 --warmup 1 > $O/bench_c4.json 2> $O/bench_c4.err || exit 1
-  timeout -k 10 400 python -u bench.py --workload c5 --steps 1 --warmup 1 > $O/bench_c5.json 2> $O/bench_c5.err || exit 1
-  JH_BENCH_DIST1=1 timeout -k 10 300 python -u -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29534 bench.py --steps 5 --warmup 1 --no-cpu --e2e 0 > $O/dist1_pool0.json 2> $O/dist1_pool0.err || exit 1
+  timeout -k 10 400 python -u bench.py --full --workload c4 --steps 3 --warmup 1 > $O/bench_c4.json 2> $O/bench_c4.err || exit 1
+  timeout -k 10 400 python -u bench.py --full --workload c5 --steps 1 --warmup 1 > $O/bench_c5.json 2> $O/bench_c5.err || exit 1
+  JH_BENCH_DIST1=1 timeout -k 10 300 python -u -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29534 bench.py --full --steps 5 --warmup 1 --no-cpu --e2e 0 > $O/dist1_pool0.json 2> $O/dist1_pool0.err || exit 1
   cd /tmp && export TMPDIR=/tmp
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/c2prof -o c2 -- python3 $R/tools/bench_c2.py --steps 5 --warmup 1 --e2e > $R/$O/bench_c2.log 2>&1 ;;
 pmc6)
