@@ -20,6 +20,7 @@
  *   jh_check_total_queue      <- (checker/total-queue) jepsen/src/jepsen/checker.clj:536-628
  *   jh_check_queue            <- (checker/queue (model/unordered-queue))
  *                                                   jepsen/src/jepsen/checker.clj:160-180
+ *   jh_check_unique_ids       <- (checker/unique-ids) jepsen/src/jepsen/checker.clj:631-676
  *
  * Plain pointers and sizes only. The caller owns every buffer; the library
  * never retains a caller pointer after returning. All entry points are
@@ -50,7 +51,7 @@
 extern "C" {
 #endif
 
-#define JH_ABI_VERSION 7
+#define JH_ABI_VERSION 8
 
 /* Return codes. Anything non-zero also writes a NUL-terminated message into
  * the caller's err buffer; the JNA shim throws ex-info and check-safe turns
@@ -536,6 +537,46 @@ int jh_check_total_queue(jh_ctx *ctx, const jh_history *h, jh_queue_result *res,
  * final_queue receives the remaining multiset when valid. */
 int jh_check_queue(jh_ctx *ctx, const jh_history *h, jh_queue_result *res,
                    int64_t *final_queue, int64_t pairs_cap, char *err, size_t errlen);
+
+/* (checker/unique-ids), checker.clj:631-676 (ABI 8), over the whole history:
+ * attempted = :invoke :generate rows; the acknowledged ids are the :value of
+ * every :ok :generate row (JH_NIL, a nil :value, is an id like any other);
+ * duplicated = the ids acknowledged more than once. :generate has no JH_F_*
+ * code of its own: it is an interned f (>= 16) like every other name, and the
+ * caller passes the code its encoder gave it in opts->f_generate.
+ *
+ * Ids are compared as signed int64, and JH_NIL (INT64_MIN) sorts first, which
+ * is where `compare` puts nil. A caller whose ids are not integers interns
+ * them; the counts and the duplicates need only equality, but range_lo /
+ * range_hi (:range) are the smallest and largest CODE, so such a caller has
+ * to intern in `compare` order if it wants :range.
+ *
+ * duplicated receives (id, count) int64 pairs: the min(duplicated_count,
+ * dup_cap) entries that (->> dups (sort-by val) reverse (take dup_cap)) keeps
+ * -- the largest counts, ties in count towards the larger id -- written in
+ * ascending id (nil first). duplicated_count is always complete.
+ * More than 2^31 - 1 acknowledged ids: JH_EUNSUPPORTED. */
+typedef struct jh_unique_ids_opts {
+    int64_t f_generate;   /* the f code the caller's encoder gave :generate (>= 0) */
+    int32_t path;         /* 0 auto, 1 dense bitmap, 2 sorted (tests force both); dense over a
+                             span above 2^35 ids (a 4 GiB bitmap) is JH_EINVAL */
+    int32_t pad;
+    int64_t reserved[4];
+} jh_unique_ids_opts;
+
+typedef struct jh_unique_ids_result {
+    int32_t valid;            /* JH_VALID / JH_INVALID */
+    int32_t path;             /* the path taken (1 / 2; 0: no acks). With only nil acks nothing
+                                 is marked or sorted: the forced path, or 1 */
+    int64_t attempted_count, acknowledged_count, duplicated_count;
+    int64_t range_lo, range_hi;   /* JH_NIL = nil */
+    int64_t nil_count;        /* acks whose id is nil */
+    double  device_ms;
+} jh_unique_ids_result;
+
+int jh_check_unique_ids(jh_ctx *ctx, const jh_history *h, const jh_unique_ids_opts *opts,
+                        jh_unique_ids_result *res, int64_t *duplicated, int64_t dup_cap,
+                        char *err, size_t errlen);
 
 #ifdef __cplusplus
 }

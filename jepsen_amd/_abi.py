@@ -6,7 +6,7 @@ every struct layout.
 """
 import ctypes as C
 
-JH_ABI_VERSION = 7
+JH_ABI_VERSION = 8
 
 JH_OK, JH_EINVAL, JH_EUNSUPPORTED, JH_EDEVICE, JH_ENOMEM = 0, 1, 2, 3, 4
 TYPE_INVOKE, TYPE_OK, TYPE_FAIL, TYPE_INFO = 0, 1, 2, 3
@@ -177,6 +177,22 @@ class JhQueueResult(C.Structure):
                 ("duplicated_count", C.c_int64), ("lost_count", C.c_int64),
                 ("recovered_count", C.c_int64), ("n_pairs", C.c_int64 * 4),
                 ("fail_entry", C.c_int64), ("fail_value", C.c_int64), ("device_ms", C.c_double)]
+
+
+UID_PATH_AUTO, UID_PATH_DENSE, UID_PATH_SORTED = 0, 1, 2
+UID_DUP_CAP = 48              # checker.clj:674: (take 48) of :duplicated
+
+
+class JhUniqueIdsOpts(C.Structure):
+    _fields_ = [("f_generate", C.c_int64), ("path", C.c_int32), ("pad", C.c_int32),
+                ("reserved", C.c_int64 * 4)]
+
+
+class JhUniqueIdsResult(C.Structure):
+    _fields_ = [("valid", C.c_int32), ("path", C.c_int32),
+                ("attempted_count", C.c_int64), ("acknowledged_count", C.c_int64),
+                ("duplicated_count", C.c_int64), ("range_lo", C.c_int64), ("range_hi", C.c_int64),
+                ("nil_count", C.c_int64), ("device_ms", C.c_double)]
 
 
 # numpy structured dtype with the same layout as jh_key_verdict

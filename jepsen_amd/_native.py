@@ -69,6 +69,8 @@ def lib():
                                                C.c_int64, C.c_char_p, C.c_size_t]
             L.jh_check_queue.argtypes = [C.c_void_p, H, C.POINTER(A.JhQueueResult), p64, C.c_int64,
                                          C.c_char_p, C.c_size_t]
+            L.jh_check_unique_ids.argtypes = [C.c_void_p, H, C.POINTER(A.JhUniqueIdsOpts),
+                                              C.POINTER(A.JhUniqueIdsResult), p64, C.c_int64, C.c_char_p, C.c_size_t]
             L.jh_host_alloc.argtypes = [C.c_size_t, C.POINTER(C.c_void_p), C.c_char_p, C.c_size_t]
             L.jh_host_free.argtypes = [C.c_void_p]
             # history ingest (include/jh_io.h), host code in the same library
@@ -102,6 +104,7 @@ EXPORTED_SYMBOLS = ["jh_version", "jh_open", "jh_open_multi", "jh_open_devices",
                     "jh_close", "jh_check_cas_independent",
                     "jh_check_cas", "jh_check_cas_independent_device", "jh_lin_configs", "jh_check_counter",
                     "jh_check_set", "jh_check_set_bitmaps", "jh_check_set_full", "jh_check_set_full_opts", "jh_check_total_queue", "jh_check_queue",
+                    "jh_check_unique_ids",
                     "jh_host_alloc", "jh_host_free",
                     # include/jh_io.h
                     "jh_ingest_file", "jh_ingest_buffer", "jh_ingest_file_opts", "jh_ingest_buffer_opts", "jh_ingest_history", "jh_ingest_time",
@@ -430,6 +433,25 @@ class Context:
         rc = lib().jh_check_queue(self._h, C.byref(h), C.byref(r), A.ptr64(pairs[0]), cap, err, len(err))
         _raise(rc, err)
         return self._queue_out(r, pairs, ["final_queue"])
+
+
+    # -- unique-ids ----------------------------------------------------------
+    def check_unique_ids(self, cols, f_generate, path=0, dup_cap=A.UID_DUP_CAP, on_device=False):
+        """jh_check_unique_ids: the result fields plus `duplicated`, a (k, 2)
+        array of (id, count) in ascending id. f_generate: the f code of
+        :generate in cols; path: 0 auto, 1 dense bitmap, 2 sorted."""
+        h = A.make_history(cols, on_device=on_device)
+        cap = max(int(dup_cap), 0)
+        pairs = np.zeros(2 * max(cap, 1), np.int64)
+        r = A.JhUniqueIdsResult()
+        o = A.JhUniqueIdsOpts(f_generate=int(f_generate), path=int(path))
+        err = C.create_string_buffer(1024)
+        rc = lib().jh_check_unique_ids(self._h, C.byref(h), C.byref(o), C.byref(r), A.ptr64(pairs), cap,
+                                       err, len(err))
+        _raise(rc, err)
+        out = {name: getattr(r, name) for name, _ in A.JhUniqueIdsResult._fields_}
+        out["duplicated"] = pairs[:2 * min(r.duplicated_count, cap)].reshape(-1, 2)
+        return out
 
 
 def _set_span_words(cols):

@@ -565,3 +565,115 @@ class TotalQueue(Checker):
 
 def total_queue():
     return TotalQueue()
+
+
+def _f_code(cols, name):
+    """The f code `encode` gave `name` in this history (KNOWN_F's spelling of
+    names: no colon); an unused code when the history has no such op."""
+    if name in H.KNOWN_F:
+        return H.KNOWN_F[name]
+    for i, x in enumerate(cols.f_names):
+        if x == name:
+            return A.F_FIRST_INTERNED + i
+    return A.F_FIRST_INTERNED + len(cols.f_names)
+
+
+def _rank_class(x):
+    if x is None:
+        return (-1, "nil")                # compare puts nil below everything
+    if isinstance(x, bool):
+        return (2, "bool")
+    if isinstance(x, (int, float, np.integer, np.floating)):
+        return (0, "number")
+    if isinstance(x, str):
+        return (1, "string")
+    return (2, type(x).__name__)
+
+
+def rank_table(table):
+    """Ranks of an interned value table in `compare` order, for ids that are
+    not integers (jh.h: :range needs codes interned in compare order; `encode`
+    interns in first-appearance order). Numbers are ordered numerically,
+    strings among strings, every other type among its own kind (by value
+    where it orders, else by first appearance); the classes are contiguous
+    and the ranks injective -- equal numbers of different types keep their
+    table order. Returns (rank, order, cls): rank[table id] = rank,
+    order[rank] = table id, cls[rank] = the class of that value."""
+    import functools
+
+    def cmp(a, b):
+        (ca, xa, ia), (cb, xb, ib) = a, b
+        if ca != cb:
+            return -1 if ca < cb else 1
+        try:
+            if xa < xb:
+                return -1
+            if xb < xa:
+                return 1
+        except TypeError:
+            pass
+        return -1 if ia < ib else (1 if ia > ib else 0)
+
+    keyed = sorted(((_rank_class(x), x, i) for i, x in enumerate(table)), key=functools.cmp_to_key(cmp))
+    order = np.asarray([i for _, _, i in keyed], np.int64).reshape(-1)
+    rank = np.empty(len(table), np.int64)
+    rank[order] = np.arange(len(table), dtype=np.int64)
+    cls = [c for c, _, _ in keyed]
+    return rank, order, cls
+
+
+class UniqueIds(Checker):
+    """(checker/unique-ids), checker.clj:631-676 (jh_check_unique_ids): every
+    :ok :generate op's :value is an id; an id acknowledged twice is a
+    duplicate. `path` forces the device path (tests): 0 auto, 1 the dense
+    bitmap, 2 the sort."""
+
+    def __init__(self, path=0, dup_cap=A.UID_DUP_CAP):
+        self.path = path
+        self.dup_cap = dup_cap
+
+    def check(self, test, history, opts):
+        import dataclasses
+        cols = _cols(history, keyed=False)
+        fgen = _f_code(cols, "generate")
+        order = cls = None
+        dcols = cols
+        if cols.values_interned:
+            # ids are value-table codes in first-appearance order: hand the
+            # device their ranks in compare order (only the :generate rows'
+            # values are ids; a set read's value is an aux offset)
+            rank, order, cls = rank_table(cols.value_table)
+            v = np.array(cols.value, dtype=np.int64, copy=True)
+            sel = (np.asarray(cols.f) == fgen) & (v != A.NIL)
+            v[sel] = rank[v[sel]]
+            dcols = dataclasses.replace(cols, value=v)
+            # acked ids of different types are not mutually comparable: the
+            # reference's (compare lowest id) throws a ClassCastException. The
+            # classes are contiguous in rank order, so the smallest and the
+            # largest non-nil acked rank tell (the device's range_lo is nil as
+            # soon as one ack is, so it cannot)
+            acked = v[sel & (np.asarray(cols.type) == A.TYPE_OK)]
+            if len(acked) and cls[int(acked.min())] != cls[int(acked.max())]:
+                raise TypeError(f"unique-ids: ids of different types are not comparable: "
+                                f"{cols.value_table[int(order[acked.min()])]!r} and "
+                                f"{cols.value_table[int(order[acked.max()])]!r}")
+        r = _ctx().check_unique_ids(dcols, fgen, path=self.path, dup_cap=self.dup_cap)
+        self.last_path = int(r["path"])
+
+        def back(x):
+            x = int(x)
+            if x == A.NIL:
+                return None
+            return cols.value_table[int(order[x])] if order is not None else x
+
+        lo, hi = int(r["range_lo"]), int(r["range_hi"])
+        return {"valid?": bool(r["valid"] == A.VALID),
+                "attempted-count": int(r["attempted_count"]),
+                "acknowledged-count": int(r["acknowledged_count"]),
+                "duplicated-count": int(r["duplicated_count"]),
+                "duplicated": {back(i): int(c) for i, c in r["duplicated"]},
+                "range": [back(lo), back(hi)]}
+
+
+def unique_ids(path=0, dup_cap=A.UID_DUP_CAP):
+    return UniqueIds(path, dup_cap)

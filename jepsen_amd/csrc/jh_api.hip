@@ -498,4 +498,19 @@ int jh_check_queue(jh_ctx *ctx, const jh_history *h, jh_queue_result *res, int64
     });
 }
 
+int jh_check_unique_ids(jh_ctx *ctx, const jh_history *h, const jh_unique_ids_opts *opts,
+                        jh_unique_ids_result *res, int64_t *duplicated, int64_t dup_cap, char *err, size_t errlen) {
+    if (!ctx || !res || !opts) { set_err(err, errlen, "null argument"); return JH_EINVAL; }
+    if (opts->f_generate < 0) { set_err(err, errlen, "f_generate < 0"); return JH_EINVAL; }
+    if (opts->path < 0 || opts->path > 2) { set_err(err, errlen, "path is 0, 1 or 2"); return JH_EINVAL; }
+    ctx = primary(ctx);
+    std::lock_guard<std::mutex> g(ctx->mu);
+    return guarded(err, errlen, [&] {
+        check_hist(h);
+        HIP_TRY(hipSetDevice(ctx->device));
+        jh_history d = stage_history(ctx, h, false, false);
+        unique_ids_check(ctx, &d, opts, res, duplicated, dup_cap < 0 ? 0 : dup_cap, ctx->stream);
+    });
+}
+
 }  // extern "C"

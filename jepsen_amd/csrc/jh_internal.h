@@ -121,6 +121,8 @@ enum WsSlot {
     WS_CFG_SLOT, WS_CFG_OUT, WS_CFG_N, WS_CFG_ROWS, WS_CFG_KEYS,
     WS_S_RB_HIST, WS_S_RB_OUT, WS_TL, WS_RS_ARENA, WS_RS_OFF, WS_RS_LOG, WS_DEFER_INFO,
     WS_SPEC, WS_SPEC_RES, WS_DEBUG_WG, WS_HANDOFF, WS_RS_LOG2,
+    WS_U_META, WS_U_PART, WS_U_LIST, WS_U_ALT, WS_U_ALT2, WS_U_BITS, WS_U_TMP, WS_U_FLAG, WS_U_RUNS, WS_U_PAIRS,
+    WS_U_CNT, WS_U_IDX, WS_U_SEL, WS_U_OUT,
     WS_COUNT
 };
 
@@ -193,3 +195,6 @@ void total_queue_check(jh_ctx *ctx, const jh_history *dh, jh_queue_result *res, 
                        int64_t cap, hipStream_t stream);
 void queue_check(jh_ctx *ctx, const jh_history *dh, jh_queue_result *res, int64_t *final_out, int64_t cap,
                  hipStream_t stream);
+// unique-ids (jh_uids.hip); dup_out = (id, count) pairs
+void unique_ids_check(jh_ctx *ctx, const jh_history *dh, const jh_unique_ids_opts *opts, jh_unique_ids_result *res,
+                      int64_t *dup_out, int64_t dup_cap, hipStream_t stream);
