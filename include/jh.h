@@ -21,6 +21,8 @@
  *   jh_check_queue            <- (checker/queue (model/unordered-queue))
  *                                                   jepsen/src/jepsen/checker.clj:160-180
  *   jh_check_unique_ids       <- (checker/unique-ids) jepsen/src/jepsen/checker.clj:631-676
+ *   jh_check_bank             <- (jepsen.tests.bank/checker opts)
+ *                                                   jepsen/src/jepsen/tests/bank.clj:46-121
  *
  * Plain pointers and sizes only. The caller owns every buffer; the library
  * never retains a caller pointer after returning. All entry points are
@@ -40,6 +42,19 @@
  *            For a set :read, the offset of its elements in `aux`.
  *   value2   for :cas the `new` element; for a set :read the element count;
  *            JH_NIL otherwise.
+ *
+ * Bank reads (jh_check_bank only; every other entry point keeps the layout
+ * above): an :ok :read whose :value is a map {account balance} has
+ *   value    the index of the read's first PAIR, value2 its number of pairs;
+ *            pair j of the read is aux[2*(value+j)] (the account code) and
+ *            aux[2*(value+j)+1] (the balance, JH_NIL = nil), in the order
+ *            (seq (:value op)) yields them; n_aux is even.
+ *   A nil :value is value = JH_NIL, value2 = 0 (the empty map).
+ *   Account codes: the caller interns accounts; code i is the i-th distinct
+ *   element of (:accounts test), any other key gets a code >= n_accounts in
+ *   first-appearance order, so "unexpected" is code < 0 || code >= n_accounts.
+ *   Ranges need not be contiguous or ordered in aux. Rows of any other f
+ *   (:transfer, nemesis) carry value = value2 = JH_NIL and are never read.
  */
 #ifndef JH_H
 #define JH_H
@@ -577,6 +592,65 @@ typedef struct jh_unique_ids_result {
 int jh_check_unique_ids(jh_ctx *ctx, const jh_history *h, const jh_unique_ids_opts *opts,
                         jh_unique_ids_result *res, int64_t *duplicated, int64_t dup_cap,
                         char *err, size_t errlen);
+
+/* (jepsen.tests.bank/checker checker-opts), tests/bank.clj:46-121 (additive to
+ * ABI 8: new structs and one new symbol), over the :ok :read rows of any
+ * process, their :value maps encoded as pair ranges (top of this file). Per
+ * read, check-op's cond gives the FIRST matching error: unexpected-key (a code
+ * outside [0, n_accounts)), nil-balance, wrong-total (the sum of the balances
+ * is not total_amount), negative-value (only when negative_balances is 0).
+ * A read without pairs sums to 0.
+ *
+ * errors[t]: per type in cond order, the number of such reads and the rows of
+ * the first, the last and the worst one. worst_badness is err-badness as an
+ * integer -- the number of unexpected keys, the number of nils, |total -
+ * total_amount| (read it as UNSIGNED 64-bit: it can reach 2^64 - 1), -(sum of
+ * the negative balances) -- and ties go to the smaller row, as util/max-by
+ * keeps the earlier element. The reference orders wrong-totals by
+ * (float (/ diff total-amount)); this result is in exact |diff| order, which
+ * is the same order while worst_badness < 2^22 (above that distinct diffs can
+ * share a float; a caller that wants the reference's tie there re-ranks the
+ * triples). lowest_row / highest_row: the wrong-total with the smallest /
+ * largest total, ties to the smaller row.
+ *
+ * reads_out (may be NULL) receives 3 * min(n_reads, reads_cap) int64:
+ * [row, total, class] per :ok :read in history order -- total is the sum of
+ * the read's non-nil balances (what bank/points plots), class 0 for no error
+ * and 1..4 for the error types, + 8 when some prefix of that sum, in pair
+ * order, overflows int64 (total is then JH_NIL). *n_reads is always complete.
+ * The reference's (reduce + balances) throws on such a prefix for a read
+ * that reaches the sum, so an overflowing read without an unexpected key or a
+ * nil (class 8) makes the call valid = JH_UNKNOWN, cause = JH_CAUSE_OVERFLOW;
+ * in a read of class 1 or 2 (9, 10) the overflow is not an error.
+ *
+ * JH_EINVAL: a pair range that leaves [0, n_aux / 2), a negative count, an
+ * odd n_aux. JH_EUNSUPPORTED: a read of more than 2^31 - 1 pairs, more than
+ * 2^31 - 2 reads. Balances that are not integers have no encoding: the shim
+ * falls back to the JVM checker. */
+typedef struct jh_bank_opts {
+    int64_t total_amount;        /* (:total-amount test) */
+    int64_t n_accounts;          /* distinct elements of (:accounts test) */
+    int32_t negative_balances;   /* (:negative-balances? checker-opts) */
+    int32_t pad;
+    int64_t reserved[4];
+} jh_bank_opts;
+
+typedef struct jh_bank_err {        /* one per type, in cond order: 0 unexpected-key, 1 nil-balance,
+                                       2 wrong-total, 3 negative-value */
+    int64_t count, first_row, last_row, worst_row, worst_badness,
+            lowest_row, highest_row; /* rows -1 when count == 0; lowest/highest: wrong-total only */
+} jh_bank_err;
+
+typedef struct jh_bank_result {
+    int32_t valid, cause;
+    int64_t read_count, error_count, first_error_row,
+            entries;                 /* pairs scanned */
+    jh_bank_err errors[4];
+    double device_ms;
+} jh_bank_result;
+
+int jh_check_bank(jh_ctx *ctx, const jh_history *h, const jh_bank_opts *opts, jh_bank_result *res,
+                  int64_t *reads_out, int64_t reads_cap, int64_t *n_reads, char *err, size_t errlen);
 
 #ifdef __cplusplus
 }

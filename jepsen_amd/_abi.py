@@ -195,6 +195,28 @@ class JhUniqueIdsResult(C.Structure):
                 ("nil_count", C.c_int64), ("device_ms", C.c_double)]
 
 
+BANK_TYPES = ("unexpected-key", "nil-balance", "wrong-total", "negative-value")   # check-op's cond order
+BANK_OVERFLOW = 8             # reads_out class bit: a prefix of the read's sum overflows
+BANK_FLOAT_EXACT = 1 << 22    # below this |diff| the float badness orders like the integer
+
+
+class JhBankOpts(C.Structure):
+    _fields_ = [("total_amount", C.c_int64), ("n_accounts", C.c_int64),
+                ("negative_balances", C.c_int32), ("pad", C.c_int32), ("reserved", C.c_int64 * 4)]
+
+
+class JhBankErr(C.Structure):
+    _fields_ = [("count", C.c_int64), ("first_row", C.c_int64), ("last_row", C.c_int64),
+                ("worst_row", C.c_int64), ("worst_badness", C.c_int64),
+                ("lowest_row", C.c_int64), ("highest_row", C.c_int64)]
+
+
+class JhBankResult(C.Structure):
+    _fields_ = [("valid", C.c_int32), ("cause", C.c_int32),
+                ("read_count", C.c_int64), ("error_count", C.c_int64), ("first_error_row", C.c_int64),
+                ("entries", C.c_int64), ("errors", JhBankErr * 4), ("device_ms", C.c_double)]
+
+
 # numpy structured dtype with the same layout as jh_key_verdict
 try:
     import numpy as _np

@@ -71,6 +71,8 @@ def lib():
                                          C.c_char_p, C.c_size_t]
             L.jh_check_unique_ids.argtypes = [C.c_void_p, H, C.POINTER(A.JhUniqueIdsOpts),
                                               C.POINTER(A.JhUniqueIdsResult), p64, C.c_int64, C.c_char_p, C.c_size_t]
+            L.jh_check_bank.argtypes = [C.c_void_p, H, C.POINTER(A.JhBankOpts), C.POINTER(A.JhBankResult), p64,
+                                        C.c_int64, p64, C.c_char_p, C.c_size_t]
             L.jh_host_alloc.argtypes = [C.c_size_t, C.POINTER(C.c_void_p), C.c_char_p, C.c_size_t]
             L.jh_host_free.argtypes = [C.c_void_p]
             # history ingest (include/jh_io.h), host code in the same library
@@ -104,7 +106,7 @@ EXPORTED_SYMBOLS = ["jh_version", "jh_open", "jh_open_multi", "jh_open_devices",
                     "jh_close", "jh_check_cas_independent",
                     "jh_check_cas", "jh_check_cas_independent_device", "jh_lin_configs", "jh_check_counter",
                     "jh_check_set", "jh_check_set_bitmaps", "jh_check_set_full", "jh_check_set_full_opts", "jh_check_total_queue", "jh_check_queue",
-                    "jh_check_unique_ids",
+                    "jh_check_unique_ids", "jh_check_bank",
                     "jh_host_alloc", "jh_host_free",
                     # include/jh_io.h
                     "jh_ingest_file", "jh_ingest_buffer", "jh_ingest_file_opts", "jh_ingest_buffer_opts", "jh_ingest_history", "jh_ingest_time",
@@ -451,6 +453,30 @@ class Context:
         _raise(rc, err)
         out = {name: getattr(r, name) for name, _ in A.JhUniqueIdsResult._fields_}
         out["duplicated"] = pairs[:2 * min(r.duplicated_count, cap)].reshape(-1, 2)
+        return out
+
+
+    # -- bank -----------------------------------------------------------------
+    def check_bank(self, cols, n_accounts, total_amount, negative_balances=False, reads_cap=None, on_device=False):
+        """jh_check_bank: the scalar result fields, `errors` (one dict per type in
+        cond order, A.BANK_TYPES), `reads` (a (k, 3) array of [row, total,
+        class] per :ok :read, k = min(n_reads, reads_cap)) and `n_reads`.
+        reads_cap None: every read."""
+        h = A.make_history(cols, on_device=on_device)
+        cap = int(cols.n) if reads_cap is None else max(int(reads_cap), 0)
+        reads = np.zeros(3 * max(cap, 1), np.int64)
+        r = A.JhBankResult()
+        o = A.JhBankOpts(total_amount=int(total_amount), n_accounts=int(n_accounts),
+                         negative_balances=1 if negative_balances else 0)
+        nr = C.c_int64()
+        err = C.create_string_buffer(1024)
+        rc = lib().jh_check_bank(self._h, C.byref(h), C.byref(o), C.byref(r), A.ptr64(reads), cap, C.byref(nr),
+                                 err, len(err))
+        _raise(rc, err)
+        out = {name: getattr(r, name) for name, _ in A.JhBankResult._fields_ if name != "errors"}
+        out["errors"] = [{name: getattr(e, name) for name, _ in A.JhBankErr._fields_} for e in r.errors]
+        out["reads"] = reads[:3 * min(nr.value, cap)].reshape(-1, 3)
+        out["n_reads"] = nr.value
         return out
 
 

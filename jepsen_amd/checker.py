@@ -677,3 +677,8 @@ class UniqueIds(Checker):
 
 def unique_ids(path=0, dup_cap=A.UID_DUP_CAP):
     return UniqueIds(path, dup_cap)
+
+
+# jepsen.tests.bank lives in its own namespace (tests/bank.clj); its checker is
+# reached as checker.bank.checker(opts), next to the names above
+from . import bank  # noqa: E402,F401

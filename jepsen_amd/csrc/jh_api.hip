@@ -513,4 +513,19 @@ int jh_check_unique_ids(jh_ctx *ctx, const jh_history *h, const jh_unique_ids_op
     });
 }
 
+int jh_check_bank(jh_ctx *ctx, const jh_history *h, const jh_bank_opts *opts, jh_bank_result *res,
+                  int64_t *reads_out, int64_t reads_cap, int64_t *n_reads, char *err, size_t errlen) {
+    if (!ctx || !res || !opts || !n_reads) { set_err(err, errlen, "null argument"); return JH_EINVAL; }
+    if (opts->n_accounts < 0) { set_err(err, errlen, "n_accounts < 0"); return JH_EINVAL; }
+    ctx = primary(ctx);
+    std::lock_guard<std::mutex> g(ctx->mu);
+    return guarded(err, errlen, [&] {
+        check_hist(h);
+        if (h->n_aux < 0 || (h->n_aux & 1)) throw_jh(JH_EINVAL, "bank: n_aux must be even and >= 0 (pairs)");
+        HIP_TRY(hipSetDevice(ctx->device));
+        jh_history d = stage_history(ctx, h, false, true);
+        bank_check(ctx, &d, opts, res, reads_out, reads_cap < 0 ? 0 : reads_cap, n_reads, ctx->stream);
+    });
+}
+
 }  // extern "C"

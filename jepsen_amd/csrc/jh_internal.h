@@ -123,6 +123,8 @@ enum WsSlot {
     WS_SPEC, WS_SPEC_RES, WS_DEBUG_WG, WS_HANDOFF, WS_RS_LOG2,
     WS_U_META, WS_U_PART, WS_U_LIST, WS_U_ALT, WS_U_ALT2, WS_U_BITS, WS_U_TMP, WS_U_FLAG, WS_U_RUNS, WS_U_PAIRS,
     WS_U_CNT, WS_U_IDX, WS_U_SEL, WS_U_OUT,
+    WS_B_META, WS_B_WORDS, WS_B_TCNT, WS_B_TBASE, WS_B_TMP, WS_B_ROW, WS_B_START, WS_B_CNT, WS_B_OFF, WS_B_TOT,
+    WS_B_BAD, WS_B_CLS, WS_B_FIRST, WS_B_PARTS, WS_B_ACC, WS_B_OUT, WS_B_TRI,
     WS_COUNT
 };
 
@@ -198,3 +200,6 @@ void queue_check(jh_ctx *ctx, const jh_history *dh, jh_queue_result *res, int64_
 // unique-ids (jh_uids.hip); dup_out = (id, count) pairs
 void unique_ids_check(jh_ctx *ctx, const jh_history *dh, const jh_unique_ids_opts *opts, jh_unique_ids_result *res,
                       int64_t *dup_out, int64_t dup_cap, hipStream_t stream);
+// bank (jh_bank.hip); reads_out = [row, total, class] triples
+void bank_check(jh_ctx *ctx, const jh_history *dh, const jh_bank_opts *opts, jh_bank_result *res,
+                int64_t *reads_out, int64_t reads_cap, int64_t *n_reads, hipStream_t stream);
