@@ -23,6 +23,8 @@
  *   jh_check_unique_ids       <- (checker/unique-ids) jepsen/src/jepsen/checker.clj:631-676
  *   jh_check_bank             <- (jepsen.tests.bank/checker opts)
  *                                                   jepsen/src/jepsen/tests/bank.clj:46-121
+ *   jh_check_long_fork        <- (jepsen.tests.long-fork/checker n)
+ *                                                   jepsen/src/jepsen/tests/long_fork.clj:158-324
  *
  * Plain pointers and sizes only. The caller owns every buffer; the library
  * never retains a caller pointer after returning. All entry points are
@@ -55,6 +57,22 @@
  *   first-appearance order, so "unexpected" is code < 0 || code >= n_accounts.
  *   Ranges need not be contiguous or ordered in aux. Rows of any other f
  *   (:transfer, nemesis) carry value = value2 = JH_NIL and are never read.
+ *
+ * Long-fork txns (jh_check_long_fork only), in the bank pair layout. f is set
+ * from the SHAPE of :value, never from the op's :f:
+ *   read txn   (every micro-op [:r k v]; nil and [] included): f = JH_F_READ,
+ *            value = the index of its first pair, value2 = its number of
+ *            pairs; pair j is aux[2*(value+j)] (the key, a signed int64) and
+ *            aux[2*(value+j)+1] (the value, JH_NIL = nil), in micro-op order.
+ *            A nil :value is value = JH_NIL, value2 = 0; an empty txn has
+ *            value2 = 0. Only :ok rows' ranges are read; ranges need not be
+ *            contiguous or ordered in aux.
+ *   write txn  (exactly one micro-op, a [:w k v]): f = JH_F_WRITE, value = k,
+ *            value2 = v.
+ *   any other row (a mixed txn, nemesis): an interned f >= 16 and value =
+ *            value2 = JH_NIL.
+ *   Keys that are not integers, and values that are not integers or nil, have
+ *   no encoding.
  */
 #ifndef JH_H
 #define JH_H
@@ -114,6 +132,8 @@ extern "C" {
                                     explored = the key's rank for the heavy-key pass, heaviest first:
                                     2^31 - 1 - its estimated inserts (the quick search's inserts over
                                     its progress, deepest layer / layers; round 5) */
+#define JH_CAUSE_MULTIPLE_WRITES 10 /* long-fork: a key written by two :invoke write txns */
+#define JH_CAUSE_ILLEGAL_HISTORY 11 /* long-fork: the reference throws :illegal-history   */
 
 #define JH_MAX_WINDOW 256
 
@@ -651,6 +671,62 @@ typedef struct jh_bank_result {
 
 int jh_check_bank(jh_ctx *ctx, const jh_history *h, const jh_bank_opts *opts, jh_bank_result *res,
                   int64_t *reads_out, int64_t reads_cap, int64_t *n_reads, char *err, size_t errlen);
+
+/* (jepsen.tests.long-fork/checker n), tests/long_fork.clj:158-324 (additive to
+ * ABI 8: new structs, two cause codes and one new symbol), over txns encoded
+ * as at the top of this file.
+ *
+ * reads = the :ok read-txn rows; early = those without a non-nil value, late =
+ * those without a nil value (a read without pairs is both). The three counts
+ * are always filled.
+ *
+ * Multiple writes: over the :invoke write-txn rows in history order, the first
+ * row whose key an earlier such row wrote -> valid = JH_UNKNOWN, cause =
+ * JH_CAUSE_MULTIPLE_WRITES, multiple_key / multiple_row; nothing below is
+ * reached then.
+ *
+ * Otherwise an :ok read whose number of pairs is not n -> valid = JH_UNKNOWN,
+ * cause = JH_CAUSE_ILLEGAL_HISTORY, illegal_kind = 1, illegal_row = the
+ * smallest such row. Reads are grouped by key set; a group that holds two
+ * distinct non-nil values for one key -> illegal_kind = 2, illegal_row = the
+ * smallest row of a read holding a value for such a key. Otherwise two reads
+ * of a group fork when each has a non-nil value where the other has nil:
+ * fork_count pairs in fork_groups groups, valid = JH_INVALID when there is one.
+ *
+ * forks_out (may be NULL) receives min(fork_count, fork_cap) [row_a, row_b]
+ * int64 pairs, row_a < row_b, ordered by group (ascending lowest key), then
+ * row_a, then row_b: the first fork_cap pairs in that order. fork_count and
+ * fork_groups are always complete.
+ *
+ * JH_EINVAL: a pair range that leaves [0, n_aux / 2), a negative count, an odd
+ * n_aux, n < 1, a forced dense path whose tables would pass 2^28 entries.
+ * JH_EUNSUPPORTED (the shim falls back): n > 64; an :ok read of exactly n pairs
+ * whose keys are not the aligned range [l, l + n), l = k - (mod k n) (group-for,
+ * the only shape the reference's generator emits), or that names one key
+ * twice (the duplicate-key test applies only to reads of exactly n pairs);
+ * more than 2^31 - 2 reads or :invoke writes. */
+typedef struct jh_long_fork_opts {
+    int64_t n;            /* the group size, 1..64 */
+    int32_t path;         /* 0 auto, 1 dense tables (indexed by key - min / group - min group),
+                             2 sparse (radix sorts); tests force both */
+    int32_t pad;
+    int64_t reserved[4];
+} jh_long_fork_opts;
+
+typedef struct jh_long_fork_result {
+    int32_t valid, cause;          /* JH_VALID / JH_INVALID / JH_UNKNOWN (cause 10 or 11) */
+    int32_t path;                  /* the path of the group slots (1 / 2; 0: the call ended before them) */
+    int32_t illegal_kind;          /* 0 none, 1 group size, 2 distinct values */
+    int64_t reads_count, early_count, late_count;
+    int64_t multiple_key, multiple_row;   /* JH_NIL / -1 when there is none */
+    int64_t illegal_row;           /* -1 when illegal_kind == 0 */
+    int64_t fork_groups, fork_count;
+    int64_t entries;               /* pairs of the :ok reads */
+    double device_ms;
+} jh_long_fork_result;
+
+int jh_check_long_fork(jh_ctx *ctx, const jh_history *h, const jh_long_fork_opts *opts, jh_long_fork_result *res,
+                       int64_t *forks_out, int64_t fork_cap, char *err, size_t errlen);
 
 #ifdef __cplusplus
 }

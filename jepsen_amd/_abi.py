@@ -28,6 +28,8 @@ CAUSES = {
     7: "overflow",
     8: "states",
     9: "deferred",
+    10: "multiple-writes",
+    11: "illegal-history",
 }
 
 MAX_WINDOW = 256
@@ -215,6 +217,26 @@ class JhBankResult(C.Structure):
     _fields_ = [("valid", C.c_int32), ("cause", C.c_int32),
                 ("read_count", C.c_int64), ("error_count", C.c_int64), ("first_error_row", C.c_int64),
                 ("entries", C.c_int64), ("errors", JhBankErr * 4), ("device_ms", C.c_double)]
+
+
+LF_PATH_AUTO, LF_PATH_DENSE, LF_PATH_SPARSE = 0, 1, 2
+LF_TILE = 4096                # rows per tile of jh_longfork.hip's scan (the tests straddle its edges)
+LF_MAX_N = 64                 # keys per group the device handles (one mask word)
+LF_DENSE_MAX = 1 << 28        # table entries above which a forced dense path is JH_EINVAL
+CAUSE_MULTIPLE_WRITES, CAUSE_ILLEGAL_HISTORY = 10, 11
+LF_ILLEGAL_GROUP_SIZE, LF_ILLEGAL_DISTINCT_VALUES = 1, 2
+
+
+class JhLongForkOpts(C.Structure):
+    _fields_ = [("n", C.c_int64), ("path", C.c_int32), ("pad", C.c_int32), ("reserved", C.c_int64 * 4)]
+
+
+class JhLongForkResult(C.Structure):
+    _fields_ = [("valid", C.c_int32), ("cause", C.c_int32), ("path", C.c_int32), ("illegal_kind", C.c_int32),
+                ("reads_count", C.c_int64), ("early_count", C.c_int64), ("late_count", C.c_int64),
+                ("multiple_key", C.c_int64), ("multiple_row", C.c_int64), ("illegal_row", C.c_int64),
+                ("fork_groups", C.c_int64), ("fork_count", C.c_int64), ("entries", C.c_int64),
+                ("device_ms", C.c_double)]
 
 
 # numpy structured dtype with the same layout as jh_key_verdict

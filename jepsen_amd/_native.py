@@ -73,6 +73,8 @@ def lib():
                                               C.POINTER(A.JhUniqueIdsResult), p64, C.c_int64, C.c_char_p, C.c_size_t]
             L.jh_check_bank.argtypes = [C.c_void_p, H, C.POINTER(A.JhBankOpts), C.POINTER(A.JhBankResult), p64,
                                         C.c_int64, p64, C.c_char_p, C.c_size_t]
+            L.jh_check_long_fork.argtypes = [C.c_void_p, H, C.POINTER(A.JhLongForkOpts),
+                                             C.POINTER(A.JhLongForkResult), p64, C.c_int64, C.c_char_p, C.c_size_t]
             L.jh_host_alloc.argtypes = [C.c_size_t, C.POINTER(C.c_void_p), C.c_char_p, C.c_size_t]
             L.jh_host_free.argtypes = [C.c_void_p]
             # history ingest (include/jh_io.h), host code in the same library
@@ -106,7 +108,7 @@ EXPORTED_SYMBOLS = ["jh_version", "jh_open", "jh_open_multi", "jh_open_devices",
                     "jh_close", "jh_check_cas_independent",
                     "jh_check_cas", "jh_check_cas_independent_device", "jh_lin_configs", "jh_check_counter",
                     "jh_check_set", "jh_check_set_bitmaps", "jh_check_set_full", "jh_check_set_full_opts", "jh_check_total_queue", "jh_check_queue",
-                    "jh_check_unique_ids", "jh_check_bank",
+                    "jh_check_unique_ids", "jh_check_bank", "jh_check_long_fork",
                     "jh_host_alloc", "jh_host_free",
                     # include/jh_io.h
                     "jh_ingest_file", "jh_ingest_buffer", "jh_ingest_file_opts", "jh_ingest_buffer_opts", "jh_ingest_history", "jh_ingest_time",
@@ -477,6 +479,23 @@ class Context:
         out["errors"] = [{name: getattr(e, name) for name, _ in A.JhBankErr._fields_} for e in r.errors]
         out["reads"] = reads[:3 * min(nr.value, cap)].reshape(-1, 3)
         out["n_reads"] = nr.value
+        return out
+
+    # -- long-fork ------------------------------------------------------------
+    def check_long_fork(self, cols, n, path=0, fork_cap=0, on_device=False):
+        """jh_check_long_fork: the result fields plus `forks`, a (k, 2) array
+        of [row_a, row_b], k = min(fork_count, fork_cap), in group / row order.
+        n: the group size; path: 0 auto, 1 dense, 2 sparse."""
+        h = A.make_history(cols, on_device=on_device)
+        cap = max(int(fork_cap), 0)
+        forks = np.zeros(2 * max(cap, 1), np.int64)
+        r = A.JhLongForkResult()
+        o = A.JhLongForkOpts(n=int(n), path=int(path))
+        err = C.create_string_buffer(1024)
+        rc = lib().jh_check_long_fork(self._h, C.byref(h), C.byref(o), C.byref(r), A.ptr64(forks), cap, err, len(err))
+        _raise(rc, err)
+        out = {name: getattr(r, name) for name, _ in A.JhLongForkResult._fields_}
+        out["forks"] = forks[:2 * min(r.fork_count, cap)].reshape(-1, 2)
         return out
 
 

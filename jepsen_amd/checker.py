@@ -682,3 +682,5 @@ def unique_ids(path=0, dup_cap=A.UID_DUP_CAP):
 # jepsen.tests.bank lives in its own namespace (tests/bank.clj); its checker is
 # reached as checker.bank.checker(opts), next to the names above
 from . import bank  # noqa: E402,F401
+# likewise jepsen.tests.long-fork (tests/long_fork.clj): checker.long_fork.checker(n)
+from . import long_fork  # noqa: E402,F401

@@ -528,4 +528,21 @@ int jh_check_bank(jh_ctx *ctx, const jh_history *h, const jh_bank_opts *opts, jh
     });
 }
 
+int jh_check_long_fork(jh_ctx *ctx, const jh_history *h, const jh_long_fork_opts *opts, jh_long_fork_result *res,
+                       int64_t *forks_out, int64_t fork_cap, char *err, size_t errlen) {
+    if (!ctx || !res || !opts) { set_err(err, errlen, "null argument"); return JH_EINVAL; }
+    if (opts->n < 1) { set_err(err, errlen, "long-fork: n < 1"); return JH_EINVAL; }
+    if (opts->path < 0 || opts->path > 2) { set_err(err, errlen, "path is 0, 1 or 2"); return JH_EINVAL; }
+    if (opts->n > 64) { set_err(err, errlen, "long-fork: groups of more than 64 keys"); return JH_EUNSUPPORTED; }
+    ctx = primary(ctx);
+    std::lock_guard<std::mutex> g(ctx->mu);
+    return guarded(err, errlen, [&] {
+        check_hist(h);
+        if (h->n_aux < 0 || (h->n_aux & 1)) throw_jh(JH_EINVAL, "long-fork: n_aux must be even and >= 0 (pairs)");
+        HIP_TRY(hipSetDevice(ctx->device));
+        jh_history d = stage_history(ctx, h, false, true);
+        long_fork_check(ctx, &d, opts, res, forks_out, fork_cap < 0 ? 0 : fork_cap, ctx->stream);
+    });
+}
+
 }  // extern "C"

@@ -125,6 +125,9 @@ enum WsSlot {
     WS_U_CNT, WS_U_IDX, WS_U_SEL, WS_U_OUT,
     WS_B_META, WS_B_WORDS, WS_B_TCNT, WS_B_TBASE, WS_B_TMP, WS_B_ROW, WS_B_START, WS_B_CNT, WS_B_OFF, WS_B_TOT,
     WS_B_BAD, WS_B_CLS, WS_B_FIRST, WS_B_PARTS, WS_B_ACC, WS_B_OUT, WS_B_TRI,
+    WS_LF_META, WS_LF_WORDS, WS_LF_TCNT, WS_LF_TBASE, WS_LF_TMP, WS_LF_ROW, WS_LF_START, WS_LF_CNT, WS_LF_GRP, WS_LF_MASK,
+    WS_LF_WKEY, WS_LF_WROW, WS_LF_FIRST, WS_LF_KEYS, WS_LF_IDX, WS_LF_RANK, WS_LF_SLOT, WS_LF_CTAB, WS_LF_VTAB, WS_LF_GBITS,
+    WS_LF_FLAG, WS_LF_SKEY, WS_LF_SMASK, WS_LF_SROW, WS_LF_PC, WS_LF_OUT,
     WS_COUNT
 };
 
@@ -203,3 +206,6 @@ void unique_ids_check(jh_ctx *ctx, const jh_history *dh, const jh_unique_ids_opt
 // bank (jh_bank.hip); reads_out = [row, total, class] triples
 void bank_check(jh_ctx *ctx, const jh_history *dh, const jh_bank_opts *opts, jh_bank_result *res,
                 int64_t *reads_out, int64_t reads_cap, int64_t *n_reads, hipStream_t stream);
+// long-fork (jh_longfork.hip); forks_out = [row_a, row_b] pairs
+void long_fork_check(jh_ctx *ctx, const jh_history *dh, const jh_long_fork_opts *opts, jh_long_fork_result *res,
+                     int64_t *forks_out, int64_t fork_cap, hipStream_t stream);

@@ -525,3 +525,149 @@ def bank_columns_to_ops(cols):
     the account table, every other row a nil :value."""
     from . import bank
     return bank.decode(cols)
+
+
+LONG_FORK_F_NAMES = ["start", "stop"]    # interned f codes 16, 17 of a long_fork_history
+LONG_FORK_STRIDE = 1_000_003             # sparse=True: group g lies at g * n * LONG_FORK_STRIDE
+
+
+def long_fork_history(n_ops=1000, n=2, n_procs=5, forks=0, repeat_write=None, sparse=False, p_info=0.02,
+                      p_fail=0.02, seed=0, tile=1):
+    """A long-fork workload for jepsen.tests.long-fork/checker
+    (tests/long_fork.clj), encoded as long_fork.encode does: `n_ops` ops of
+    `n_procs` processes, an invocation row and a completion row each,
+    interleaved. It follows the reference generator's state machine
+    (long_fork.clj:114-156): a process that has just written a key reads that
+    key's group; otherwise, with probability 1/2, it reads the group of a key
+    some process wrote last; otherwise it writes a fresh key (value 1). A
+    write takes effect when it completes (:ok always, :info half of the time,
+    :fail never) and an :ok read sees exactly the keys in effect, in shuffled
+    key order, so the history has no fork. Completions are :fail / :info with
+    probability p_fail / p_info. Every 500th op is a nemesis :info :start /
+    :stop pair instead.
+
+    forks: that many forks are planted at even distances, each in a fresh
+    group of its own by one extra process: two keys written, then two :ok reads
+    that each see one of them (n >= 2). repeat_write: the op number at which
+    the extra process writes, once more, the first key written so far.
+    sparse: groups lie LONG_FORK_STRIDE groups apart. Groups start seven
+    below zero, so keys are negative too. tile: the whole history repeated
+    that many times with disjoint keys (bench sizes; forks and the repeated
+    write repeat with it). Returns Columns; n_ops * tile ops."""
+    import random
+    from . import _abi as A
+    from .history import Columns
+    if forks and n < 2:
+        raise ValueError("a fork needs a group of at least 2 keys")
+    rng = random.Random(seed)
+    proc, typ, fc, val, val2, aux = [], [], [], [], [], []
+    mul = LONG_FORK_STRIDE if sparse else 1
+
+    def key(k):
+        return (k // n - 7) * n * mul + k % n
+
+    def emit(p, t, f, v=-(1 << 63), v2=-(1 << 63)):
+        proc.append(p); typ.append(t); fc.append(f); val.append(v); val2.append(v2)
+
+    def emit_read(p, t, ks=None, seen=()):
+        if ks is None:
+            emit(p, t, A.F_READ, A.NIL, 0)
+            return
+        emit(p, t, A.F_READ, len(aux) // 2, len(ks))
+        for k in ks:
+            aux.extend((key(k), 1 if k in seen else A.NIL))
+
+    def group(k):
+        ks = list(range(k - k % n, k - k % n + n))
+        rng.shuffle(ks)
+        return ks
+
+    state = {"next": 0, "first": None}
+
+    def fresh():
+        k = state["next"]
+        state["next"] += 1
+        if state["first"] is None:
+            state["first"] = k
+        return k
+
+    extra = n_procs
+    plant_at = {(i + 1) * n_ops // (forks + 1) for i in range(forks)}
+    workers, pending, applied = {}, {}, set()
+    started = 0
+    while started < n_ops or pending:
+        p = rng.randrange(n_procs)
+        if p in pending:
+            kind, x = pending.pop(p)
+            u = rng.random()
+            t = A.TYPE_FAIL if u < p_fail else A.TYPE_INFO if u < p_fail + p_info else A.TYPE_OK
+            if kind == "w":
+                if t == A.TYPE_OK or (t == A.TYPE_INFO and rng.random() < 0.5):
+                    applied.add(x)
+                emit(p, t, A.F_WRITE, key(x), 1)
+            elif t == A.TYPE_OK:
+                emit_read(p, t, x, applied)
+            else:
+                emit_read(p, t)
+            continue
+        if started >= n_ops:
+            continue
+        if started in plant_at:
+            plant_at.discard(started)
+            state["next"] += -state["next"] % n                  # a group of its own
+            ks = [fresh() for _ in range(n)]
+            for k in ks[:2]:
+                emit(extra, A.TYPE_INVOKE, A.F_WRITE, key(k), 1)
+                emit(extra, A.TYPE_OK, A.F_WRITE, key(k), 1)
+            for k in ks[:2]:
+                emit_read(extra, A.TYPE_INVOKE)
+                emit_read(extra, A.TYPE_OK, group(k), {k})
+        if repeat_write is not None and started == repeat_write:
+            k = fresh() if state["first"] is None else state["first"]
+            emit(extra, A.TYPE_INVOKE, A.F_WRITE, key(k), 1)
+            emit(extra, A.TYPE_OK, A.F_WRITE, key(k), 1)
+            if state["next"] == 1 and k == 0 and len(fc) == 2:     # nothing was written before: write it twice
+                emit(extra, A.TYPE_INVOKE, A.F_WRITE, key(k), 1)
+                emit(extra, A.TYPE_OK, A.F_WRITE, key(k), 1)
+        started += 1
+        if started % 500 == 0:
+            emit(-1, A.TYPE_INFO, A.F_FIRST_INTERNED + (started // 500) % 2)
+            emit(-1, A.TYPE_INFO, A.F_FIRST_INTERNED + (started // 500) % 2)
+            continue
+        k = workers.get(p)
+        if k is not None:
+            workers[p] = None
+            pending[p] = ("r", group(k))
+            emit_read(p, A.TYPE_INVOKE)
+            continue
+        active = [x for x in workers.values() if x is not None]
+        if rng.random() < 0.5 and active:
+            pending[p] = ("r", group(rng.choice(active)))
+            emit_read(p, A.TYPE_INVOKE)
+        else:
+            k = fresh()
+            workers[p] = k
+            pending[p] = ("w", k)
+            emit(p, A.TYPE_INVOKE, A.F_WRITE, key(k), 1)
+    cols = [np.asarray(c, np.int64) for c in (proc, typ, fc, val, val2)]
+    auxa = np.asarray(aux, np.int64)
+    if tile > 1:
+        span = (state["next"] + n + (-state["next"]) % n) * mul          # keys per copy, a multiple of n
+        rows, half = len(proc), len(aux) // 2
+        is_w = cols[2] == A.F_WRITE
+        is_r = (cols[2] == A.F_READ) & (cols[3] != A.NIL)
+        shift = np.repeat(np.arange(tile, dtype=np.int64), rows)
+        cols = [np.tile(c, tile) for c in cols]
+        cols[3] = cols[3] + np.where(np.tile(is_w, tile), shift * span, 0) + np.where(np.tile(is_r, tile), shift * half, 0)
+        auxa = np.tile(auxa, tile)
+        auxa[0::2] += np.repeat(np.arange(tile, dtype=np.int64), half) * span
+    N = len(cols[0])
+    return Columns(n=N, process=cols[0], type=cols[1], f=cols[2], key=np.full(N, -1, np.int64), value=cols[3],
+                   value2=cols[4], n_keys=0, aux=auxa, f_names=list(LONG_FORK_F_NAMES))
+
+
+def long_fork_columns_to_ops(cols):
+    """Op maps (with :index) of a long-fork history's Columns, for the
+    restatements (jepsen_amd/long_fork.py decode)."""
+    from . import long_fork
+    return long_fork.decode(cols)

@@ -11,6 +11,8 @@
      linear_tutorial.json  doc/tutorial/04-checker.md:126-138 (the printed
                         :linear analysis; its history is elided there and
                         reconstructed here)
+     long_fork.json     jepsen/test/jepsen/tests/long_fork_test.clj:7-20 (history
+                        and expected map; micro-ops as ["r", k, v])
 2. Seeded synthetic vectors (synthetic_*.npz + manifest.json): small
    histories from jepsen_amd.synth with the CPU oracle's verdicts, each
    cross-checked against the knossos-style WGL and (for tiny keys) brute
@@ -340,16 +342,42 @@ def linear_tutorial():
             "model": {"cas-register": None}, "algorithm": "linear", "history": hist, "expected": expected}
 
 
+def long_fork():
+    """jepsen/test/jepsen/tests/long_fork_test.clj:7-20 (checker-test),
+    transcribed: keywords become strings, the ops carry what the test's maps
+    carry (:type :f :value)."""
+    def r(*kv): return [["r", k, v] for k, v in kv]
+    r1 = {"type": "invoke", "f": "read", "value": r((0, None), (1, None), (2, None))}
+    r1c = {"type": "ok", "f": "read", "value": r((0, 1), (1, 1), (2, None))}
+    r2 = {"type": "invoke", "f": "read", "value": r((2, None), (0, None), (1, None))}
+    r2c = {"type": "ok", "f": "read", "value": r((2, 1), (0, 1), (1, None))}
+    return {"source": "jepsen/test/jepsen/tests/long_fork_test.clj:7-20", "n": 3, "history": [r1, r2, r1c, r2c],
+            "expected": {"valid?": False, "early-read-count": 0, "late-read-count": 0, "reads-count": 2,
+                         "forks": [[r1c, r2c]]}}
+
+
+LONG_FORK_MANIFEST = {"name": "long_fork", "file": "long_fork.json",
+                      "source": "jepsen/test/jepsen/tests/long_fork_test.clj:7-20", "n": 3, "rows": 4, "forks": 1}
+
+
+def write_long_fork_manifest():
+    """The fixture's manifest line, in a file of its own: manifest.json lists
+    the synthetic vectors only and stays as it is."""
+    with open(os.path.join(GOLD, "manifest_long_fork.json"), "w") as f:
+        json.dump({"generated_by": "tools/make_golden.py", "reference": [LONG_FORK_MANIFEST]}, f, indent=1)
+
+
 def main():
     os.makedirs(GOLD, exist_ok=True)
     for name, fn in [("perf_test", perf_test), ("counter", counter), ("interval_str", interval_str),
                      ("independent", independent), ("set_full", set_full),
-                     ("queue", queue), ("linear_tutorial", linear_tutorial)]:
+                     ("queue", queue), ("linear_tutorial", linear_tutorial), ("long_fork", long_fork)]:
         with open(os.path.join(GOLD, name + ".json"), "w") as f:
             json.dump(fn(), f, indent=1)
     man = synthetic()
     with open(os.path.join(GOLD, "manifest.json"), "w") as f:
         json.dump({"generated_by": "tools/make_golden.py", "synthetic": man}, f, indent=1)
+    write_long_fork_manifest()
     print("wrote", GOLD)
 
 
@@ -357,5 +385,9 @@ if __name__ == "__main__":
     if "--linear-tutorial" in sys.argv:       # this fixture alone (no reference tree needed)
         with open(os.path.join(GOLD, "linear_tutorial.json"), "w") as f:
             json.dump(linear_tutorial(), f, indent=1)
+    elif "--long-fork" in sys.argv:           # this fixture and its manifest line alone
+        with open(os.path.join(GOLD, "long_fork.json"), "w") as f:
+            json.dump(long_fork(), f, indent=1)
+        write_long_fork_manifest()
     else:
         main()
