@@ -546,8 +546,11 @@ int jh_check_set_full_opts(jh_ctx *ctx, const jh_history *h, const int64_t *time
 
 /* Queues. Values are the :value of :enqueue / :dequeue ops and the elements
  * of :ok :drain ops (integers, or ids the shim interned; JH_NIL = nil).
- * Multisets come back as (value, multiplicity) int64 pairs sorted by value,
- * at most pairs_cap pairs per multiset (n_pairs is always complete). */
+ * Multisets come back as (value, multiplicity) int64 pairs in ascending
+ * order of value, with nil's pair (value JH_NIL) last, after every integer --
+ * not first, where its INT64_MIN encoding would sort. At most pairs_cap
+ * pairs are written per multiset, a prefix in that order (n_pairs is always
+ * complete), so a multiset cut short loses nil's pair first. */
 typedef struct jh_queue_result {
     int32_t valid;             /* JH_VALID / JH_INVALID */
     int32_t cause;
