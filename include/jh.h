@@ -222,11 +222,14 @@ typedef struct jh_lin_opts {
     /* scheduling of the heavy-key pass (every value decides the same verdicts;
      * the parity tests run the less common paths through these): */
     int32_t helpers;           /* phase-2 late helper workgroups; <=0: 64 (a quarter of the CUs), at most half the CUs (JH_LIN_NO_HELPERS: none) */
-    int32_t helper_late_us;    /* run time before a helper takes a key; <=0: 250 (JH_LIN_HELPERS_NOW: 0) */
+    int32_t helper_late_us;    /* > 0: a helper takes the key running longest, once past this run time
+                                  (JH_LIN_HELPERS_NOW: at once; JH_LIN_HELP_STALL: 250); <=0: the pick
+                                  by stall, helper_stall_min */
     int32_t xw_waves;          /* waves of the 65-256-member search; <=0: one per key, up to 4 per CU */
-    int32_t p2_waves_per_cu;   /* 1: phase 2 at one wave per CU with the 128 KB LDS memo; else 4,
-                                  or 3 with the 16 KB Bloom filter when LEAN keys run alone
-                                  (round 5) */
+    int32_t p2_waves_per_cu;   /* 1: phase 2 at one wave per CU with the 128 KB LDS memo; else 4
+                                  when WIDE keys share the grid. LEAN keys alone: 3 (32 KB memo,
+                                  16 KB Bloom filter, round 5) or 6 (16 KB memo, 8 KB filter,
+                                  round 7); <=0: the default, DESIGN.md section 5 */
     int32_t lean_waves;        /* at most this many phase-2 waves for LEAN keys; <=0: no cap */
     int32_t wide_waves;        /* at most this many waves for WIDE keys; <=0: no cap */
     int32_t handover_min;      /* phase 1: once its queue is empty, searches past this many
@@ -235,7 +238,12 @@ typedef struct jh_lin_opts {
                                   the deferred searches resume, round 5; else off), <0: never */
     int32_t p1_waves_per_cu;   /* phase-1 waves per CU (<= 26, the LDS limit); <=0: 26 */
     int32_t bfs_wgs;           /* ABI 7: phase-2 reachable-set BFS workgroups (one per CU); <=0: default */
-    int32_t reserved2;
+    int32_t helper_stall_min;  /* round 7 (the former reserved slot): a late helper takes a key once its
+                                  sequential search has made this many inserts without reaching a
+                                  deeper layer (published every 1024 inserts), the smallest such
+                                  stall first; <=0: 4096. Not used when helper_late_us > 0 or
+                                  JH_LIN_HELPERS_NOW / JH_LIN_HELP_STALL is set: those keep the
+                                  time-based pick */
 } jh_lin_opts;
 
 #define JH_DEFAULT_BUDGET (1 << 20)

@@ -81,7 +81,7 @@ class JhLinOpts(C.Structure):
                 ("xw_waves", C.c_int32), ("p2_waves_per_cu", C.c_int32),
                 ("lean_waves", C.c_int32), ("wide_waves", C.c_int32),
                 ("handover_min", C.c_int32), ("p1_waves_per_cu", C.c_int32),
-                ("bfs_wgs", C.c_int32), ("reserved2", C.c_int32)]       # ABI 7
+                ("bfs_wgs", C.c_int32), ("helper_stall_min", C.c_int32)]       # ABI 7 (round 7: its reserved slot)
 
 
 # every field of jh_key_verdict: the parity tests compare all of them

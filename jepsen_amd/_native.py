@@ -122,7 +122,7 @@ def _raise(rc, err):
 
 def _opts(init, budget, stream=0, algorithm=None, exact_count=True, **tune):
     """jh_lin_opts. tune: flags, quick_budget, phase2_budget, helpers,
-    helper_late_us, xw_waves, p2_waves_per_cu (jh.h; all decide the same
+    helper_late_us, helper_stall_min, xw_waves, p2_waves_per_cu (jh.h; all decide the same
     verdicts, the tests use them to reach the less common search paths).
     exact_count: JH_LIN_EXACT_COUNT, WGL's cache size for every key (what the
     parity tests compare with the oracle); the checkers pass False -- their
@@ -136,7 +136,7 @@ def _opts(init, budget, stream=0, algorithm=None, exact_count=True, **tune):
         algorithm = A.ALGORITHMS[algorithm]
     o.algorithm = int(algorithm or 0)
     for k, v in tune.items():
-        if k not in dict(A.JhLinOpts._fields_) or k in ("init_value", "budget", "stream", "algorithm", "reserved", "reserved2"):
+        if k not in dict(A.JhLinOpts._fields_) or k in ("init_value", "budget", "stream", "algorithm", "reserved"):
             raise TypeError(f"unknown jh_lin_opts field {k}")
         setattr(o, k, int(v))
     if exact_count:

@@ -24,6 +24,7 @@
 #include "jh_internal.h"
 #include <hipcub/hipcub.hpp>
 #include <algorithm>
+#include <type_traits>
 
 namespace {
 
@@ -88,6 +89,19 @@ using MemoM = MemoCfg<10, 15>;   // very heavy keys: 32 KB memo + 4 KB Bloom = 3
 #define JH_P2_PER_CU 3
 #endif
 using MemoP2 = MemoCfg<JH_P2_LG, JH_P2_BLOOM>;
+// round 7, the dense instance of the same role (p2_waves_per_cu = 6): 16 KB
+// memo + 8 KB Bloom filter, 24.5 KB per wave, six waves per CU. Twice the
+// searches in flight drain phase 2's queue sooner (C3 rank 0: 15.7 -> 7.6 ms
+// after phase 2 begins); each has half the LDS memo
+constexpr int P2_DENSE_PER_CU = 6;
+using MemoP2D = MemoCfg<9, 16>;
+// The default for LEAN-only grids. It pays only together with the helpers'
+// pick by stall (HELPER_STALL_MIN): C3 rank 0, medians of alternating runs,
+// 37.9 ms (round 6) -> 36.1 ms with both, 37.6 ms at three per CU with the
+// pick by stall, 38.4 ms at six per CU with the pick by run time; rank 4
+// 43.0 -> 43.7 ms (inside its 1.5 ms spread), C4 202.7 -> 199.8 ms.
+// profiles/r07/phase2_sched/, DESIGN.md section 5
+constexpr int P2_LEAN_PER_CU = P2_DENSE_PER_CU;
 constexpr int STATE_BITS = 20, T_BITS = 20, GEN_BITS = 24;
 constexpr uint32_t STATE_MASK = (1u << STATE_BITS) - 1, T_MASK = (1u << T_BITS) - 1;
 
@@ -335,6 +349,10 @@ struct DfsArgs {
     // whenever its deepest layer advances, so the late helpers pick the keys
     // stuck longest (a big dead subtree) rather than the ones running longest
     int32_t stamp_progress;
+    // round 7: per key, the inserts the sequential search has made since its
+    // deepest layer last rose (or since its resume), published at its periodic
+    // check (every 1024 inserts); wg_helper_pick's default policy reads it
+    uint32_t *stall;
     // JH_DEFER_TIMES=1 (timeline study): [0] first wave start, [1] last wave
     // end (s_memrealtime), [2 + key] the time the key was handed on
     unsigned long long *defer_time;
@@ -508,6 +526,18 @@ constexpr int32_t P1_PRIO_INS = 0;
 // 32.6 / 24.9 / 21.1 ms; 96 leaves the sequential search too few CUs)
 constexpr int HELPERS = 64;
 constexpr uint64_t HELPER_LATE_US = 250;
+// Round 7: helpers take keys by the stall their sequential search publishes
+// (inserts since its deepest layer last rose), the smallest stall past
+// HELPER_STALL_MIN first: the newest crosser is a valid key inside a dead
+// subtree, where the acceleration and the spec board pay; the largest stalls
+// belong to the invalid keys, whose stall never ends and which the BFS settles.
+// On C3 rank 0, 157 keys ever reach a stall of 4 096 (the 72 invalid ones and
+// 85 valid ones), 638 reach 2 048 (tools/shape/stall_study.py). Compared once
+// with 2 048: rank 0 34.5 ms against 36.1, but rank 4 45.6 against 43.7 (the
+// parent: 43.0), so 4 096 stays. At most HELPER_MAINS helpers run keys; the
+// others serve the spec board only.
+constexpr uint32_t HELPER_STALL_MIN = 4096;
+constexpr int HELPER_MAINS = 32;
 
 // write a key's verdict; in a race only the first finisher writes
 __device__ __forceinline__ bool emit_verdict(jh_key_verdict *out, int32_t *claim, int key,
@@ -1523,6 +1553,10 @@ __device__ __forceinline__ int dfs_lean(const DfsArgs &A, const KeyInfo &K, cons
     wave_sync();
     uint32_t ins_saved = 0xFFFFFFFFu;     // a handed-over search's real insert count
     uint32_t nlog = 0;                    // hlog entries (saturating at 0xFFFF)
+    // round 7 (A.stall): the insert count at the resume, or at the first
+    // periodic check that saw a deeper tmax (kept in the check block alone, so
+    // the published stall is up to 1023 inserts short of the true one)
+    uint32_t stall_base = 0, stall_tmax = 0;
     bool ho = false;                      // a late helper takes this search over (A.handoff)
     unsigned long long ho_off = 0;        // its record's place, reserved when the request is accepted
     // move the window forward from layer t to layer nt (a lift, or a resume)
@@ -1598,6 +1632,7 @@ __device__ __forceinline__ int dfs_lean(const DfsArgs &A, const KeyInfo &K, cons
                 tmax = max((uint32_t)(h_dt >> 32), t);
                 r = lay_hi(t) & 63;
                 rn = t + 1 < n_ok ? (lay_hi(t + 1) & 63) : 0;
+                stall_base = ins; stall_tmax = tmax;
             }
         }
     }
@@ -1691,6 +1726,13 @@ insert:
                 if (ins >= 4u * (uint32_t)A.prio_ins) __builtin_amdgcn_s_setprio(3);
                 else if (ins >= 2u * (uint32_t)A.prio_ins) __builtin_amdgcn_s_setprio(2);
                 else __builtin_amdgcn_s_setprio(1);
+            }
+            // (compiled out of phase 1's instance, MemoQ: its registers are capped)
+            if (!std::is_same<M, MemoQ>::value && A.stall) {
+                // round 7: publish the stall for the late helpers' pick
+                if (tmax > stall_tmax) { stall_tmax = tmax; stall_base = ins; }
+                if (lane == 0)
+                    __hip_atomic_store(&A.stall[key], ins - stall_base, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
             if (HO && A.handoff) {
                 // round 6: a late helper asks for this search (the takeover);
@@ -2828,6 +2870,10 @@ struct WgArgs {
     int32_t spec_first;        // helpers serve the board before taking keys (JH_LIN_SPEC_FIRST)
     int32_t n_mains;           // helpers [n_mains, grid) only serve the board (never take a key)
     int32_t *mains_live;       // helpers running a key now (the board's servers stay while any does)
+    // round 7: the sequential searches' published stalls (null: the pick by
+    // run time, late_ticks) and the least stall at which a helper takes a key
+    const uint32_t *stall;
+    uint32_t stall_min;
 };
 
 __device__ __forceinline__ uint64_t lk_make(uint32_t t, uint32_t s, uint64_t m) {
@@ -3930,6 +3976,8 @@ done:
 // (too large for the BFS) and a long backtracking DFS, which otherwise holds
 // the whole step on one wave. Sets sh.key (-1: the sequential search has
 // left its queue, or the helper has waited HELPER_MAX_TICKS: done).
+// Round 7 (W.stall, the default): the key is picked by its search's published
+// stall instead of its run time (HELPER_STALL_MIN above).
 constexpr unsigned long long HELPER_MAX_TICKS = 500000000ULL;   // 5 s of s_memrealtime (100 MHz)
 #ifndef JH_HELP_BY_ORDER
 #define JH_HELP_BY_ORDER 0
@@ -4003,10 +4051,17 @@ __device__ void wg_helper_pick(const WgArgs &W, WgShared &sh, int tid, unsigned 
             const int key = A.live_n ? ld_agent(&A.list[i]) : A.list[i];
             if (key < 0) continue;
             const unsigned long long s = __hip_atomic_load(&W.seq_start[key], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (s == 0 || s == SEQ_HANDED || s > now || now - s < W.late_ticks) continue;
+            if (s == 0 || s == SEQ_HANDED || s > now || (!W.stall && now - s < W.late_ticks)) continue;
             if (__hip_atomic_load(&A.claim[key], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ||
                 __hip_atomic_load(&W.taken[key], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
                 continue;
+            if (W.stall) {
+                // round 7: a key whose search has stalled for stall_min
+                // inserts or more, the smallest stall (the newest crosser) first
+                const uint32_t stl = __hip_atomic_load(&W.stall[key], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (stl >= W.stall_min) atomicMin(&sh.pick, ((unsigned long long)stl << 24) | (unsigned long long)i);
+                continue;
+            }
             const unsigned long long run = min(now - s, (1ULL << 40) - 1);
             // JH_HELP_BY_ORDER: the first key in the list's order (least
             // phase-1 progress first) among those past the delay; else the
@@ -7053,6 +7108,8 @@ void lin_check_independent(jh_ctx *ctx, const jh_history *dh, const jh_lin_opts 
     DfsArgs b{};
     WgArgs wr{}, wh{};
     unsigned long long *seq_start = nullptr;
+    uint32_t *seq_stall = nullptr;
+    int p2_per_cu = P2_LEAN_PER_CU;
     bool p2_m = true, bfs_only = false;
     auto prep_race = [&](int nd_all, int nd_l) {
         claim = ctx->ws<int32_t>(WS_CLAIM, K);
@@ -7155,8 +7212,12 @@ void lin_check_independent(jh_ctx *ctx, const jh_history *dh, const jh_lin_opts 
         cap2l = cap2;
         if (nd_l > 0) {
             const int cus2 = std::max(1, ctx->n_cu - wg2 - help_cus);
-            // LEAN keys alone in the grid: MemoP2's waves per CU
-            const int lean_per_cu = n_def_w > 0 || !p2_small_ok ? 4 : JH_P2_PER_CU;
+            // LEAN keys alone in the grid: MemoP2's waves per CU, or the dense
+            // instance's (round 7; p2_waves_per_cu = 3 / 6 selects one)
+            p2_per_cu = P2_LEAN_PER_CU;
+            if (opts && (opts->p2_waves_per_cu == JH_P2_PER_CU || opts->p2_waves_per_cu == P2_DENSE_PER_CU))
+                p2_per_cu = opts->p2_waves_per_cu;
+            const int lean_per_cu = n_def_w > 0 || !p2_small_ok ? 4 : p2_per_cu;
             int want2 = std::min(nd_l, cus2 * (p2_m ? lean_per_cu : 1));
             if (opts && opts->lean_waves > 0) want2 = std::min(want2, opts->lean_waves);
             const uint64_t fixed = (uint64_t)stack_cap * sizeof(Frame) + scr_bytes_h;
@@ -7165,11 +7226,11 @@ void lin_check_independent(jh_ctx *ctx, const jh_history *dh, const jh_lin_opts 
             waves3 = waves2;
             // more keys than waves: phase 2 stops at p2 inserts and phase 3
             // takes the rest on full tables, so phase 2's LEAN role can run
-            // JH_P2_PER_CU waves per CU on tables for 2 x p2 entries
+            // p2_per_cu waves per CU on tables for 2 x p2 entries
             if (p2_m && p2_small_ok && n_def_w == 0 && !(opts && opts->lean_waves > 0) && budget > p2) {
                 uint32_t cs = 1u << 16;
                 while ((int64_t)cs < 2 * p2 && cs < cap2) cs <<= 1;
-                const int want_s = std::min(nd_l, cus2 * JH_P2_PER_CU);
+                const int want_s = std::min(nd_l, cus2 * p2_per_cu);
                 const int ws = fit_units(ctx, want_s, (uint64_t)cs * 16 + fixed, {WS_MEMO_DEEP, WS_STACK_DEEP, WS_SCRATCH_DEEP});
                 if (ws < nd_l) {
                     cap2l = cs;
@@ -7191,19 +7252,29 @@ void lin_check_independent(jh_ctx *ctx, const jh_history *dh, const jh_lin_opts 
         if (wg_race && nd_l > 0) wr = build_wg(std::max(1, ctx->n_cu - wg2), claim, q + 6);
         wh = WgArgs{};
         seq_start = nullptr;
+        seq_stall = nullptr;
         if (n_help > 0) {
             const bool spec_on = !(lflags & JH_LIN_NO_SPEC) && !(tune_env("JH_SPEC") && !atoi(tune_env("JH_SPEC")));
             wh = build_wg(n_help, claim, nullptr, spec_on);
             seq_start = ctx->ws<unsigned long long>(WS_HELP_START, K);
-            int32_t *taken = ctx->ws<int32_t>(WS_HELP_TAKEN, K);
+            // [0, K): the taken flags; [K, 2K): the sequential searches' stalls (round 7)
+            int32_t *taken = ctx->ws<int32_t>(WS_HELP_TAKEN, 2 * (size_t)K);
             HIP_TRY(hipMemsetAsync(seq_start, 0, (size_t)K * sizeof(unsigned long long), st));
-            HIP_TRY(hipMemsetAsync(taken, 0, (size_t)K * sizeof(int32_t), st));
+            HIP_TRY(hipMemsetAsync(taken, 0, 2 * (size_t)K * sizeof(int32_t), st));
+            seq_stall = (uint32_t *)(taken + K);
             wh.seq_start = seq_start; wh.seq_exit = q + 28; wh.seq_waves = waves2; wh.taken = taken;
             wh.mains_live = q + Q_MAINS;
             uint64_t late_us = HELPER_LATE_US;
             if (opts && opts->helper_late_us > 0) late_us = (uint64_t)opts->helper_late_us;
             if (lflags & JH_LIN_HELPERS_NOW) late_us = 0;
             wh.late_ticks = late_us * 100;     // s_memrealtime: 100 MHz
+            // round 7, the default pick: by the sequential search's published
+            // stall (wg_helper_pick); a caller that sets a delay or one of the
+            // round-6 policies keeps the pick by run time
+            const bool by_time = JH_HELP_BY_ORDER || (opts && opts->helper_late_us > 0) ||
+                                 (lflags & (JH_LIN_HELPERS_NOW | JH_LIN_HELP_STALL));
+            wh.stall = by_time ? nullptr : seq_stall;
+            wh.stall_min = opts && opts->helper_stall_min > 0 ? (uint32_t)opts->helper_stall_min : HELPER_STALL_MIN;
             // round 6: the spec board (SpecSlot), unless JH_LIN_NO_SPEC
             if (spec_on) {
                 wh.spec = ctx->ws<SpecSlot>(WS_SPEC, SPEC_SLOTS);
@@ -7213,7 +7284,11 @@ void lin_check_independent(jh_ctx *ctx, const jh_history *dh, const jh_lin_opts 
                 wh.spec_min = 512; wh.spec_mult = 32; wh.spec_dist = 128;
                 wh.spec_q = q + Q_SPEC;
                 wh.spec_first = (lflags & JH_LIN_SPEC_FIRST) ? 1 : 0;
-                wh.n_mains = n_wg;
+                // round 7: at most HELPER_MAINS helpers run keys; the others
+                // serve the board from the start, so a main's first posts find
+                // servers (with every helper a main, the board was served only
+                // by helpers between keys)
+                wh.n_mains = std::min(n_wg, HELPER_MAINS);
                 if (const char *e = tune_env("JH_SPEC_SERVERS")) wh.n_mains = std::max(1, n_wg - std::max(0, atoi(e)));
                 if (const char *e = tune_env("JH_SPEC_MIN")) wh.spec_min = (uint32_t)std::max(1, atoi(e));
                 if (const char *e = tune_env("JH_SPEC_MULT")) wh.spec_mult = (uint32_t)std::max(1, atoi(e));
@@ -7241,6 +7316,7 @@ void lin_check_independent(jh_ctx *ctx, const jh_history *dh, const jh_lin_opts 
         b.probes = (unsigned long long *)(q + 8);
         b.seq_start = seq_start; b.exit_count = seq_start ? q + 28 : nullptr;
         b.stamp_progress = seq_start && (lflags & JH_LIN_HELP_STALL) ? 1 : 0;
+        b.stall = seq_stall;
         b.defer_time = nullptr;
         // round 6, the takeover: a late helper continues the sequential
         // search's record (phase 2's own slot log, 32 K entries per wave)
@@ -7400,7 +7476,7 @@ void lin_check_independent(jh_ctx *ctx, const jh_history *dh, const jh_lin_opts 
                 DfsArgs c3 = b;
                 c3.list = defer3; c3.n_list = 0; c3.n_list_dev = q + 16; c3.defer = 0; c3.live_n = nullptr;
                 c3.defer_list = nullptr; c3.defer_count = nullptr;
-                c3.seq_start = nullptr; c3.exit_count = nullptr; c3.t_span = nullptr; c3.wave_off = 0;
+                c3.seq_start = nullptr; c3.exit_count = nullptr; c3.stall = nullptr; c3.t_span = nullptr; c3.wave_off = 0;
                 c3.budget = budget; c3.budget_full = 0; c3.handoff = nullptr;
                 c3.gen_base = ctx->gen_base + 2 * (uint32_t)K + 1;
                 c3.dbg = nullptr;
@@ -7696,6 +7772,8 @@ void lin_check_independent(jh_ctx *ctx, const jh_history *dh, const jh_lin_opts 
                 pr.l = b; pr.w = bw; pr.n_l = waves2;
                 pr.w.wave_off = waves2;
                 if (n_def_w > 0) k_lin_seq_lw<false, MemoM><<<waves2 + waves_w, 64, SEQLW_LDS, ctx->aux>>>(pr);
+                else if (p2_per_cu == P2_DENSE_PER_CU && p2_small_ok)
+                    k_lin_seq_lw<false, MemoP2D><<<waves2, 64, MemoP2D::LDS, ctx->aux>>>(pr);
                 else k_lin_seq_lw<false, MemoP2><<<waves2, 64, MemoP2::LDS, ctx->aux>>>(pr);
                 wide_done = true;
             } else if (waves2) k_lin_seq<true><<<waves2, 64, MemoH::LDS, ctx->aux>>>(b);
@@ -7719,7 +7797,7 @@ void lin_check_independent(jh_ctx *ctx, const jh_history *dh, const jh_lin_opts 
                 DfsArgs c3 = b;
                 c3.list = defer3; c3.n_list = 0; c3.n_list_dev = q + 16; c3.defer = 0;
                 c3.defer_list = nullptr; c3.defer_count = nullptr;
-                c3.seq_start = nullptr; c3.exit_count = nullptr;
+                c3.seq_start = nullptr; c3.exit_count = nullptr; c3.stall = nullptr;
                 c3.budget = budget; c3.budget_full = 0; c3.handoff = nullptr;
                 c3.memo_cap = cap2;
                 c3.gen_base = ctx->gen_base + 2 * (uint32_t)K + 1;
