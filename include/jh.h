@@ -506,16 +506,21 @@ int jh_host_free(void *p);
  * it, last-present / last-absent = the read INVOCATION of greatest index
  * whose :ok read did / did not contain it; all counted from the element's
  * last :invoke :add on (a re-invoke resets its state, checker.clj:483-487).
- * The lost / never-read / stale element lists come back sorted, at most
- * list_cap each (the counts are always complete); worst_stale holds the
- * (take 8 (reverse (sort-by :stable-latency stale))) entries. */
+ * A read counts as the set of its elements: their order, repeated elements,
+ * JH_NIL entries and values that no integer process ever added (below,
+ * above or between the elements) do not matter.
+ * The lost / never-read / stale element lists come back sorted; with fewer
+ * than count entries of room (list_cap) each is the sorted list's prefix,
+ * and the counts, quantiles and worst_stale are always those of the whole
+ * result. worst_stale holds the (take 8 (reverse (sort-by :stable-latency
+ * stale))) entries: among equal latencies the larger element first. */
 #define JH_SF_QUANTILES 5          /* points [0 0.5 0.95 0.99 1], checker.clj:412 */
 #define JH_SF_WORST 8
 
 typedef struct jh_set_full_elem {
     int64_t element;
     int64_t stable_latency;        /* ms */
-    int64_t known_entry;           /* row of the :known op */
+    int64_t known_entry;           /* row of the :known op: an :ok :add or an :ok :read */
     int64_t last_absent_entry;     /* row of the :last-absent read invocation, or -1 */
 } jh_set_full_elem;
 
