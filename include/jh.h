@@ -136,6 +136,23 @@ extern "C" {
 #define JH_CAUSE_ILLEGAL_HISTORY 11 /* long-fork: the reference throws :illegal-history   */
 
 #define JH_MAX_WINDOW 256
+/* Per-key limits, each pinned at N and N + 1 by tests/test_gpu_lin_edges.py:
+ *  - a widest window of 257 members or more: JH_UNKNOWN / JH_CAUSE_WINDOW;
+ *  - 2^20 - 1 or more :ok ops that the search keeps (not failed, not a read of
+ *    nil): JH_UNKNOWN / JH_CAUSE_WINDOW for that key alone, explored = 0
+ *    (2^20 - 2 are searched);
+ *  - more than 65532 distinct values in one key, the initial value included:
+ *    JH_UNKNOWN / JH_CAUSE_STATES for that key alone, explored = 0.
+ * The value range is taken over the whole call: vmax - vmin over every client
+ * read / write / cas value and the initial value. One outlying value in one
+ * key therefore decides for every key whether states fit 8 bits (vmax - vmin
+ * <= 254: the LDS memo of windows up to 40), whether the reachable-set engine
+ * applies (vmax - vmin <= 4093; with JH_ALGO_LINEAR the analyzer is
+ * JH_ANALYZER_LINEAR exactly for the searched keys of at most 32 window members
+ * then, and fewer than 2^20 - 2 ok ops), and whether values are numbered per
+ * key (vmax - vmin >= 65531, or a difference that overflows int64; the two
+ * conditions above then read "the largest key's distinct values" + 1 for
+ * vmax - vmin + 2). Verdicts, causes, rows and explored do not depend on it. */
 
 typedef struct jh_history {
     int64_t n;                 /* entries */

@@ -6045,16 +6045,20 @@ __device__ void xw_dump_configs(const XwArgs &A, const uint64_t *memo, uint32_t 
             if ((uint32_t)(e4 >> 40) != gen || ((uint32_t)(e4 >> 20) & T_MASK) != tmax) continue;
             offer(Cfg5{(uint32_t)e4 & STATE_MASK, SL == 4 ? e[3] : 0ULL, SL == 4 ? e[2] : 0ULL, e[1], e[0]});
         }
-        // wave minimum of the lanes' best
-        for (int o = 32; o > 0; o >>= 1) {
-            Cfg5 x;
-            x.s = (uint32_t)__shfl_xor((int)best.s, o);
-            x.m3 = (uint64_t)__shfl_xor((long long)best.m3, o); x.m2 = (uint64_t)__shfl_xor((long long)best.m2, o);
-            x.m1 = (uint64_t)__shfl_xor((long long)best.m1, o); x.m0 = (uint64_t)__shfl_xor((long long)best.m0, o);
-            const bool xh = __shfl_xor((int)have, o) != 0;
-            if (xh && (!have || cfg_less(x, best))) { best = x; have = true; }
+        // wave minimum of the lanes' best: the lowest lane still in is the
+        // pivot, broadcast from scalar registers; the lanes holding a smaller
+        // one stay in. The last pivot is the minimum, the same in every lane.
+        uint64_t in = ballot(have);
+        if (!in) break;
+        while (in) {
+            const int l = __builtin_ctzll(in);
+            Cfg5 pv;
+            pv.s = (uint32_t)readlane((int)best.s, l);
+            pv.m3 = readlane64(best.m3, l); pv.m2 = readlane64(best.m2, l);
+            pv.m1 = readlane64(best.m1, l); pv.m0 = readlane64(best.m0, l);
+            in = ballot(((in >> lane) & 1) && cfg_less(best, pv));
+            if (!in) best = pv;
         }
-        if (!have) break;
         prev = best;
         n = i + 1;
         const long long val = cfg_state_value(best.s, A.per_key_values, A.vmin, A.init_value, A.src, s0, s1,
