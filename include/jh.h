@@ -25,6 +25,8 @@
  *                                                   jepsen/src/jepsen/tests/bank.clj:46-121
  *   jh_check_long_fork        <- (jepsen.tests.long-fork/checker n)
  *                                                   jepsen/src/jepsen/tests/long_fork.clj:158-324
+ *   jh_check_causal_reverse   <- (independent/checker (jepsen.tests.causal-reverse/checker))
+ *                                                   jepsen/src/jepsen/tests/causal_reverse.clj:21-84
  *
  * Plain pointers and sizes only. The caller owns every buffer; the library
  * never retains a caller pointer after returning. All entry points are
@@ -73,6 +75,13 @@
  *            value2 = JH_NIL.
  *   Keys that are not integers, and values that are not integers or nil, have
  *   no encoding.
+ *
+ * Causal-reverse (jh_check_causal_reverse only): the standard columns. A
+ * :write has f = JH_F_WRITE and value = the written integer (never JH_NIL); an
+ * :ok :read has f = JH_F_READ, value = the offset of its elements in aux and
+ * value2 = their number (the set-read layout; a nil or empty :value has
+ * value2 = 0, and then value is not looked at). `key` as in
+ * jh_check_cas_independent; key == NULL or n_keys == 0 is one un-keyed history.
  */
 #ifndef JH_H
 #define JH_H
@@ -760,6 +769,66 @@ typedef struct jh_long_fork_result {
 
 int jh_check_long_fork(jh_ctx *ctx, const jh_history *h, const jh_long_fork_opts *opts, jh_long_fork_result *res,
                        int64_t *forks_out, int64_t fork_cap, char *err, size_t errlen);
+
+/* (independent/checker (jepsen.tests.causal-reverse/checker)),
+ * tests/causal_reverse.clj:21-84 (additive to ABI 8: new structs and one new
+ * symbol), batched over the keys of an independent history.
+ *
+ * Per key: the rows with f = JH_F_WRITE of type :invoke / :ok (any process)
+ * build the precedence graph; every :ok JH_F_READ row is then judged, wherever
+ * it stands. With last_inv[v] the row of the last :invoke of v and first_ok[v]
+ * the row of the first :ok of v (invoked or not), a read that saw the set S has
+ * M = max last_inv[w] over the invoked w in S (none: -1), expects
+ * E = {v : first_ok[v] < M} and is an error when E - S is not empty:
+ * expected_count = |E|, missing = E - S. S is the SET of the read's elements:
+ * repeated elements change nothing. (The reference's behaviour on a vector
+ * :value, clojure.set/difference testing indices, is not reproduced here; the
+ * shim keeps such reads on the host unless asked otherwise.)
+ *
+ * key_valid (may be NULL) receives max(n_keys, 1) int32: JH_VALID / JH_INVALID.
+ * errors_out (may be NULL) receives the first min(error_count, err_cap) failing
+ * reads in row order as 5 int64 each: [row, key, expected_count, missing_count,
+ * missing_offset] (key 0 for an un-keyed history; missing_offset = the sum of
+ * the missing_count of the failing reads before it). missing_out (may be NULL)
+ * receives the first min(missing_total, missing_cap) values of the failing
+ * reads' missing sets, each ascending, concatenated in that same order. Every
+ * result field is complete whatever the caps are.
+ *
+ * Two tiers. A key with at most JH_CR_LDS_VALUES distinct written values is
+ * judged by one workgroup that keeps the key's value table in LDS; any other
+ * key runs the same kernel with its table in device memory. The scratch of the
+ * global tier is bounded by JH_CR_SCRATCH_MAX bytes: beyond it JH_ENOMEM.
+ *
+ * JH_EINVAL: an :ok read's range that leaves [0, n_aux), a negative count, a
+ * key >= n_keys, path 1 forced with a key of more than JH_CR_LDS_VALUES
+ * distinct values. JH_EUNSUPPORTED (the shim falls back): in a keyed history
+ * an :invoke / :ok write row or an :ok read row without a key (it would belong
+ * to every key); a write of JH_NIL; more than 2^31 - 2 reads or writes. */
+#define JH_CR_LDS_VALUES 1024            /* distinct values per key of the on-chip tier */
+#define JH_CR_SCRATCH_MAX (1LL << 32)    /* bytes of value tables and bitmaps of the global tier */
+
+typedef struct jh_causal_reverse_opts {
+    int32_t path;         /* 0 auto, 1 on-chip per-key tier, 2 global tier; tests force both */
+    int32_t pad;
+    int64_t reserved[4];
+} jh_causal_reverse_opts;
+
+typedef struct jh_causal_reverse_result {
+    int32_t valid, cause;          /* JH_VALID / JH_INVALID; cause is JH_CAUSE_NONE */
+    int32_t path;                  /* 1: every key on chip, 2: some key in the global tier, 0: no key was judged */
+    int32_t pad;
+    int64_t read_count;            /* :ok reads */
+    int64_t error_count;           /* failing reads */
+    int64_t invalid_keys;
+    int64_t first_error_row;       /* -1 when there is none */
+    int64_t missing_total;         /* sum of missing_count over the failing reads */
+    int64_t entries;               /* elements of the :ok reads */
+    double device_ms;
+} jh_causal_reverse_result;
+
+int jh_check_causal_reverse(jh_ctx *ctx, const jh_history *h, const jh_causal_reverse_opts *opts,
+                            jh_causal_reverse_result *res, int32_t *key_valid, int64_t *errors_out, int64_t err_cap,
+                            int64_t *missing_out, int64_t missing_cap, char *err, size_t errlen);
 
 #ifdef __cplusplus
 }

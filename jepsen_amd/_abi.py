@@ -239,6 +239,21 @@ class JhLongForkResult(C.Structure):
                 ("device_ms", C.c_double)]
 
 
+CR_PATH_AUTO, CR_PATH_LDS, CR_PATH_GLOBAL = 0, 1, 2
+CR_LDS_VALUES = 1024          # JH_CR_LDS_VALUES: distinct values per key of the on-chip tier
+
+
+class JhCausalReverseOpts(C.Structure):
+    _fields_ = [("path", C.c_int32), ("pad", C.c_int32), ("reserved", C.c_int64 * 4)]
+
+
+class JhCausalReverseResult(C.Structure):
+    _fields_ = [("valid", C.c_int32), ("cause", C.c_int32), ("path", C.c_int32), ("pad", C.c_int32),
+                ("read_count", C.c_int64), ("error_count", C.c_int64), ("invalid_keys", C.c_int64),
+                ("first_error_row", C.c_int64), ("missing_total", C.c_int64), ("entries", C.c_int64),
+                ("device_ms", C.c_double)]
+
+
 # numpy structured dtype with the same layout as jh_key_verdict
 try:
     import numpy as _np

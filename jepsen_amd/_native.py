@@ -75,6 +75,9 @@ def lib():
                                         C.c_int64, p64, C.c_char_p, C.c_size_t]
             L.jh_check_long_fork.argtypes = [C.c_void_p, H, C.POINTER(A.JhLongForkOpts),
                                              C.POINTER(A.JhLongForkResult), p64, C.c_int64, C.c_char_p, C.c_size_t]
+            L.jh_check_causal_reverse.argtypes = [C.c_void_p, H, C.POINTER(A.JhCausalReverseOpts),
+                                                  C.POINTER(A.JhCausalReverseResult), C.POINTER(C.c_int32), p64,
+                                                  C.c_int64, p64, C.c_int64, C.c_char_p, C.c_size_t]
             L.jh_host_alloc.argtypes = [C.c_size_t, C.POINTER(C.c_void_p), C.c_char_p, C.c_size_t]
             L.jh_host_free.argtypes = [C.c_void_p]
             # history ingest (include/jh_io.h), host code in the same library
@@ -108,7 +111,7 @@ EXPORTED_SYMBOLS = ["jh_version", "jh_open", "jh_open_multi", "jh_open_devices",
                     "jh_close", "jh_check_cas_independent",
                     "jh_check_cas", "jh_check_cas_independent_device", "jh_lin_configs", "jh_check_counter",
                     "jh_check_set", "jh_check_set_bitmaps", "jh_check_set_full", "jh_check_set_full_opts", "jh_check_total_queue", "jh_check_queue",
-                    "jh_check_unique_ids", "jh_check_bank", "jh_check_long_fork",
+                    "jh_check_unique_ids", "jh_check_bank", "jh_check_long_fork", "jh_check_causal_reverse",
                     "jh_host_alloc", "jh_host_free",
                     # include/jh_io.h
                     "jh_ingest_file", "jh_ingest_buffer", "jh_ingest_file_opts", "jh_ingest_buffer_opts", "jh_ingest_history", "jh_ingest_time",
@@ -496,6 +499,32 @@ class Context:
         _raise(rc, err)
         out = {name: getattr(r, name) for name, _ in A.JhLongForkResult._fields_}
         out["forks"] = forks[:2 * min(r.fork_count, cap)].reshape(-1, 2)
+        return out
+
+    # -- causal-reverse -------------------------------------------------------
+    def check_causal_reverse(self, cols, path=0, err_cap=0, missing_cap=0, on_device=False, key_valid=True):
+        """jh_check_causal_reverse: the result fields plus `key_valid` (int32
+        per key, max(n_keys, 1) of them; None when not asked for), `errors`, a
+        (k, 5) array of [row, key, expected_count, missing_count,
+        missing_offset], k = min(error_count, err_cap), in row order, and
+        `missing`, the first min(missing_total, missing_cap) missing values. A
+        cap of 0 passes a NULL pointer. path: 0 auto, 1 on-chip, 2 global."""
+        h = A.make_history(cols, on_device=on_device)
+        ecap, mcap = max(int(err_cap), 0), max(int(missing_cap), 0)
+        errs = np.zeros(5 * ecap, np.int64) if ecap else None
+        miss = np.zeros(mcap, np.int64) if mcap else None
+        kv = np.full(max(int(cols.n_keys), 1), -1, np.int32) if key_valid else None
+        r = A.JhCausalReverseResult()
+        o = A.JhCausalReverseOpts(path=int(path))
+        err = C.create_string_buffer(1024)
+        rc = lib().jh_check_causal_reverse(self._h, C.byref(h), C.byref(o), C.byref(r),
+                                           kv.ctypes.data_as(C.POINTER(C.c_int32)) if key_valid else None,
+                                           A.ptr64(errs), ecap, A.ptr64(miss), mcap, err, len(err))
+        _raise(rc, err)
+        out = {name: getattr(r, name) for name, _ in A.JhCausalReverseResult._fields_ if name != "pad"}
+        out["key_valid"] = kv
+        out["errors"] = (errs[:5 * min(r.error_count, ecap)] if ecap else np.zeros(0, np.int64)).reshape(-1, 5)
+        out["missing"] = miss[:min(r.missing_total, mcap)] if mcap else np.zeros(0, np.int64)
         return out
 
 

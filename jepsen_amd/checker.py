@@ -684,3 +684,5 @@ def unique_ids(path=0, dup_cap=A.UID_DUP_CAP):
 from . import bank  # noqa: E402,F401
 # likewise jepsen.tests.long-fork (tests/long_fork.clj): checker.long_fork.checker(n)
 from . import long_fork  # noqa: E402,F401
+# and jepsen.tests.causal-reverse (tests/causal_reverse.clj): checker.causal_reverse.checker()
+from . import causal_reverse  # noqa: E402,F401

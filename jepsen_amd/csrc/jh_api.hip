@@ -545,4 +545,22 @@ int jh_check_long_fork(jh_ctx *ctx, const jh_history *h, const jh_long_fork_opts
     });
 }
 
+int jh_check_causal_reverse(jh_ctx *ctx, const jh_history *h, const jh_causal_reverse_opts *opts,
+                            jh_causal_reverse_result *res, int32_t *key_valid, int64_t *errors_out, int64_t err_cap,
+                            int64_t *missing_out, int64_t missing_cap, char *err, size_t errlen) {
+    if (!ctx || !res || !opts) { set_err(err, errlen, "null argument"); return JH_EINVAL; }
+    if (opts->path < 0 || opts->path > 2) { set_err(err, errlen, "path is 0, 1 or 2"); return JH_EINVAL; }
+    ctx = primary(ctx);
+    std::lock_guard<std::mutex> g(ctx->mu);
+    return guarded(err, errlen, [&] {
+        check_hist(h);
+        if (h->n_aux < 0) throw_jh(JH_EINVAL, "causal-reverse: n_aux < 0");
+        HIP_TRY(hipSetDevice(ctx->device));
+        const bool keyed = h->key != nullptr && h->n_keys > 0;
+        jh_history d = stage_history(ctx, h, keyed, true);
+        if (!keyed) d.key = nullptr;
+        causal_reverse_check(ctx, &d, opts, res, key_valid, errors_out, err_cap, missing_out, missing_cap, ctx->stream);
+    });
+}
+
 }  // extern "C"

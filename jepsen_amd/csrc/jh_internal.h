@@ -128,6 +128,8 @@ enum WsSlot {
     WS_LF_META, WS_LF_WORDS, WS_LF_TCNT, WS_LF_TBASE, WS_LF_TMP, WS_LF_ROW, WS_LF_START, WS_LF_CNT, WS_LF_GRP, WS_LF_MASK,
     WS_LF_WKEY, WS_LF_WROW, WS_LF_FIRST, WS_LF_KEYS, WS_LF_IDX, WS_LF_RANK, WS_LF_SLOT, WS_LF_CTAB, WS_LF_VTAB, WS_LF_GBITS,
     WS_LF_FLAG, WS_LF_SKEY, WS_LF_SMASK, WS_LF_SROW, WS_LF_PC, WS_LF_OUT,
+    WS_CR_META, WS_CR_WORDS, WS_CR_TCNT, WS_CR_TBASE, WS_CR_TMP, WS_CR_WKEY, WS_CR_WVAL, WS_CR_RKEY, WS_CR_RPERM, WS_CR_RROW,
+    WS_CR_OFF, WS_CR_TIER, WS_CR_KV, WS_CR_EXP, WS_CR_MISS, WS_CR_SOFF, WS_CR_SCRATCH, WS_CR_OUT, WS_CR_SEG, WS_CR_MBUF,
     WS_COUNT
 };
 
@@ -209,3 +211,7 @@ void bank_check(jh_ctx *ctx, const jh_history *dh, const jh_bank_opts *opts, jh_
 // long-fork (jh_longfork.hip); forks_out = [row_a, row_b] pairs
 void long_fork_check(jh_ctx *ctx, const jh_history *dh, const jh_long_fork_opts *opts, jh_long_fork_result *res,
                      int64_t *forks_out, int64_t fork_cap, hipStream_t stream);
+// causal-reverse (jh_causal.hip); errors_out = [row, key, expected_count, missing_count, missing_offset]
+void causal_reverse_check(jh_ctx *ctx, const jh_history *dh, const jh_causal_reverse_opts *opts,
+                          jh_causal_reverse_result *res, int32_t *key_valid, int64_t *errors_out, int64_t err_cap,
+                          int64_t *missing_out, int64_t missing_cap, hipStream_t stream);

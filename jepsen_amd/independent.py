@@ -3,12 +3,15 @@
 `checker(inner)` lifts a checker over [k v] tuples. When the inner checker
 is (or composes) a cas-register `linearizable`, the whole history is encoded
 once and ALL keys are checked by one libjh call (splitter + per-key WGL on
-the GPU); any other composed checkers still run per key on their own.
+the GPU); any other composed checkers still run per key on their own. When it
+is (or composes) a causal-reverse checker, every key's reads are judged by one
+jh_check_causal_reverse call in the same way.
 """
 from . import _abi as A
 from . import history as H
 from .checker import (Checker, Compose, Linearizable, _algorithm, add_configs, check_safe, lin_result, merge_valid,
                       wants_configs, _init_state, _ctx)
+from .causal_reverse import CausalReverseChecker, check_independent as _cr_check_independent
 from .model import to_device_ops
 
 DIR = "independent"
@@ -97,6 +100,16 @@ def _lin_member(inner):
     return None, None
 
 
+def _cr_member(inner):
+    if isinstance(inner, CausalReverseChecker):
+        return None, inner
+    if isinstance(inner, Compose):
+        for name, c in inner.checker_map.items():
+            if isinstance(c, CausalReverseChecker):
+                return name, c
+    return None, None
+
+
 class IndependentChecker(Checker):
     """independent.clj:247-298."""
 
@@ -159,6 +172,21 @@ class IndependentChecker(Checker):
                                               for x in r.values())
                     results[key] = r
                 return self._results_map(results)
+        cr_name, cr = _cr_member(self.inner) if lin is None else (None, None)
+        cr_res = _cr_check_independent(cr, history) if cr is not None else None
+        if cr_res is not None:
+            if cr_name is None:
+                return self._results_map(cr_res)
+            results = {}
+            subs = subhistories(history, list(cr_res))
+            for key, res in cr_res.items():
+                r = {}
+                for nm, c in self.inner.checker_map.items():
+                    r[nm] = res if nm == cr_name else check_safe(
+                        c, test, subs[key], {"subdirectory": [DIR, key], "history-key": key})
+                r["valid?"] = merge_valid(x.get("valid?") if isinstance(x, dict) else None for x in r.values())
+                results[key] = r
+            return self._results_map(results)
         # generic path: every key through the inner checker (per-key device
         # calls for a linearizable inner)
         results = {}

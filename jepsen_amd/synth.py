@@ -671,3 +671,122 @@ def long_fork_columns_to_ops(cols):
     restatements (jepsen_amd/long_fork.py decode)."""
     from . import long_fork
     return long_fork.decode(cols)
+
+
+# ---------------------------------------------------------------------------
+# causal-reverse ("sequential") workload, jepsen/src/jepsen/tests/causal_reverse.clj:100-111
+def _causal_reverse_key(rng, ops, n_procs, p_info, n_viol):
+    """One key's rows (process, type, f, value, value2; a read's value is its
+    offset into the key's own elements) and its elements. Writes of 0, 1, 2, ...
+    and reads, mixed evenly over n_procs processes; an :ok read returns every
+    completed write plus a random subset of the writes in flight (:info writes
+    stay in flight for good). A violating read shows one write and omits one
+    that completed before that write's invoke."""
+    from . import _abi as A
+    rows, aux, n_aux = [], [], 0
+    done = []                        # completed writes, in completion order
+    flying = []                      # invoked, not (yet) completed
+    before = {}                      # write -> how many of `done` were complete at its invoke
+    pending = [None] * n_procs
+    nxt, invoked = 0, 0
+    while invoked < ops or any(x is not None for x in pending):
+        p = int(rng.integers(n_procs))
+        cur = pending[p]
+        if cur is None:
+            if invoked >= ops:
+                continue
+            invoked += 1
+            if rng.random() < 0.5:
+                pending[p] = ("r", None)
+                rows.append((p, A.TYPE_INVOKE, A.F_READ, A.NIL, 0))
+            else:
+                pending[p] = ("w", nxt)
+                before[nxt] = len(done)
+                flying.append(nxt)
+                rows.append((p, A.TYPE_INVOKE, A.F_WRITE, nxt, A.NIL))
+                nxt += 1
+            continue
+        pending[p] = None
+        info = rng.random() < p_info
+        if cur[0] == "w":
+            if info:
+                rows.append((p, A.TYPE_INFO, A.F_WRITE, cur[1], A.NIL))
+            else:
+                flying.remove(cur[1])
+                done.append(cur[1])
+                rows.append((p, A.TYPE_OK, A.F_WRITE, cur[1], A.NIL))
+            continue
+        if info:
+            rows.append((p, A.TYPE_INFO, A.F_READ, A.NIL, 0))
+            continue
+        seen = np.asarray(done + [x for x in flying if rng.random() < 0.5], np.int64)
+        if n_viol > 0:
+            shown = [x for x in seen.tolist() if before[x] > 0]
+            if shown:
+                x = shown[int(rng.integers(len(shown)))]
+                gone = done[int(rng.integers(before[x]))]
+                if gone != x:
+                    seen = seen[seen != gone]
+                    n_viol -= 1
+        rng.shuffle(seen)
+        rows.append((p, A.TYPE_OK, A.F_READ, n_aux, len(seen)))
+        aux.append(seen)
+        n_aux += len(seen)
+    return np.asarray(rows, np.int64).reshape(-1, 5), (np.concatenate(aux) if aux else np.zeros(0, np.int64))
+
+
+def causal_reverse_history(n_keys=64, ops_per_key=500, n_procs=5, violations=0, p_info=0.02, seed=0, tile=1,
+                           concurrent=4):
+    """A keyed causal-reverse history as Columns (key ids 0 .. n_keys * tile -
+    1, `keys` the same numbers): ops_per_key invocations per key, `concurrent`
+    keys interleaved at a time as independent/concurrent-generator runs them.
+    violations: reads made to violate the write order (at most; spread over
+    random keys, each key's at its first reads that can). tile: the block of
+    n_keys keys is repeated with fresh key ids and element ranges of its own
+    (large benchmark histories; violations are then per block)."""
+    from . import _abi as A
+    rng = np.random.default_rng(seed)
+    viol = np.bincount(rng.integers(n_keys, size=violations), minlength=n_keys) if violations else np.zeros(n_keys, int)
+    parts = [_causal_reverse_key(rng, ops_per_key, n_procs, p_info, int(viol[k])) for k in range(n_keys)]
+    counts = np.asarray([len(r) for r, _ in parts], np.int64)
+    aux_base = np.concatenate([[0], np.cumsum([len(a) for _, a in parts])]).astype(np.int64)
+    N = int(counts.sum())
+    out = np.empty((N, 5), np.int64)
+    keycol = np.empty(N, np.int64)
+    at = 0
+    for g0 in range(0, n_keys, concurrent):
+        ks = np.arange(g0, min(g0 + concurrent, n_keys))
+        label = np.repeat(ks, counts[ks])
+        rng.shuffle(label)
+        slots = at + np.argsort(label, kind="stable")         # key by key, each key's slots ascending
+        s0 = 0
+        for k in ks:
+            rows = parts[k][0].copy()
+            rd = (rows[:, 2] == A.F_READ) & (rows[:, 1] == A.TYPE_OK)
+            rows[rd, 3] += aux_base[k]
+            sl = slots[s0:s0 + counts[k]]
+            out[sl] = rows
+            keycol[sl] = k
+            s0 += counts[k]
+        at += len(label)
+    auxa = np.concatenate([a for _, a in parts]) if parts else np.zeros(0, np.int64)
+    if len(auxa) == 0:
+        auxa = np.zeros(1, np.int64)
+    if tile > 1:
+        rd = np.tile((out[:, 2] == A.F_READ) & (out[:, 1] == A.TYPE_OK), tile)
+        shift = np.repeat(np.arange(tile, dtype=np.int64), N)
+        keycol = np.tile(keycol, tile) + shift * n_keys
+        n_aux = len(auxa)
+        out = np.tile(out, (tile, 1))
+        out[:, 3] += np.where(rd, shift * n_aux, 0)
+        auxa = np.tile(auxa, tile)
+    K = n_keys * tile
+    return Columns(n=len(out), process=out[:, 0].copy(), type=out[:, 1].copy(), f=out[:, 2].copy(), key=keycol,
+                   value=out[:, 3].copy(), value2=out[:, 4].copy(), n_keys=K, aux=auxa, keys=list(range(K)))
+
+
+def causal_reverse_columns_to_ops(cols):
+    """Op maps of a causal-reverse history's Columns (independent tuples for
+    keyed rows; jepsen_amd/causal_reverse.py decode)."""
+    from . import causal_reverse
+    return causal_reverse.decode(cols)

@@ -13,6 +13,9 @@
                         reconstructed here)
      long_fork.json     jepsen/test/jepsen/tests/long_fork_test.clj:7-20 (history
                         and expected map; micro-ops as ["r", k, v])
+     causal_reverse.json  jepsen/test/jepsen/tests/causal_reverse_test.clj:10-58 (the
+                        six histories and the :valid? the test asserts; reads
+                        are vectors, as there)
 2. Seeded synthetic vectors (synthetic_*.npz + manifest.json): small
    histories from jepsen_amd.synth with the CPU oracle's verdicts, each
    cross-checked against the knossos-style WGL and (for tiny keys) brute
@@ -367,17 +370,52 @@ def write_long_fork_manifest():
         json.dump({"generated_by": "tools/make_golden.py", "reference": [LONG_FORK_MANIFEST]}, f, indent=1)
 
 
+def causal_reverse():
+    """jepsen/test/jepsen/tests/causal_reverse_test.clj:10-58, transcribed:
+    knossos.op's (invoke p f v) / (ok p f v) as maps, the read :value vectors as
+    lists, and what the test asserts of (:valid? (checker/check ...))."""
+    def inv(f, v): return {"process": 0, "type": "invoke", "f": f, "value": v}
+    def ok(f, v): return {"process": 0, "type": "ok", "f": f, "value": v}
+
+    def sequential(vs, seen):
+        h = []
+        for v in vs:
+            h += [inv("write", v), ok("write", v)]
+        return h + [inv("read", None), ok("read", seen)]
+    cases = [("valid", sequential([1, 2], [1, 2]), True),
+             ("one-without-two", sequential([1, 2], [1]), True),
+             ("two-without-one", sequential([1, 2], [2]), False),
+             ("bigger", sequential([1, 2, 3, 4, 5], [1, 2, 3, 4, 5]), True),
+             ("concurrent1", [inv("write", 2), inv("write", 1), ok("write", 1), inv("read", None), ok("write", 2),
+                              ok("read", [1, 2])], True),
+             ("concurrent2", [inv("write", 1), inv("write", 2), ok("write", 1), inv("read", None), ok("write", 2),
+                              ok("read", [2, 1])], True)]
+    return {"source": "jepsen/test/jepsen/tests/causal_reverse_test.clj:10-58",
+            "cases": [{"name": n, "history": h, "valid?": v} for n, h, v in cases]}
+
+
+def write_causal_reverse_manifest():
+    g = causal_reverse()
+    with open(os.path.join(GOLD, "manifest_causal_reverse.json"), "w") as f:
+        json.dump({"generated_by": "tools/make_golden.py", "reference": [
+            {"name": "causal_reverse", "file": "causal_reverse.json", "source": g["source"],
+             "cases": [{"name": c["name"], "rows": len(c["history"]), "valid?": c["valid?"]} for c in g["cases"]]}]},
+            f, indent=1)
+
+
 def main():
     os.makedirs(GOLD, exist_ok=True)
     for name, fn in [("perf_test", perf_test), ("counter", counter), ("interval_str", interval_str),
                      ("independent", independent), ("set_full", set_full),
-                     ("queue", queue), ("linear_tutorial", linear_tutorial), ("long_fork", long_fork)]:
+                     ("queue", queue), ("linear_tutorial", linear_tutorial), ("long_fork", long_fork),
+                     ("causal_reverse", causal_reverse)]:
         with open(os.path.join(GOLD, name + ".json"), "w") as f:
             json.dump(fn(), f, indent=1)
     man = synthetic()
     with open(os.path.join(GOLD, "manifest.json"), "w") as f:
         json.dump({"generated_by": "tools/make_golden.py", "synthetic": man}, f, indent=1)
     write_long_fork_manifest()
+    write_causal_reverse_manifest()
     print("wrote", GOLD)
 
 
@@ -389,5 +427,9 @@ if __name__ == "__main__":
         with open(os.path.join(GOLD, "long_fork.json"), "w") as f:
             json.dump(long_fork(), f, indent=1)
         write_long_fork_manifest()
+    elif "--causal-reverse" in sys.argv:      # likewise
+        with open(os.path.join(GOLD, "causal_reverse.json"), "w") as f:
+            json.dump(causal_reverse(), f, indent=1)
+        write_causal_reverse_manifest()
     else:
         main()
