@@ -7,6 +7,7 @@
 for gfx950 without a GPU. Objects are rebuilt only when a source or header is
 newer.
 """
+import glob
 import os
 import subprocess
 import sys
@@ -19,6 +20,8 @@ OBJ = os.path.join(HERE, "build")
 HIP_SOURCES = ["jh_lin.hip", "jh_counter.hip", "jh_set.hip", "jh_setfull.hip", "jh_queue.hip", "jh_uids.hip", "jh_bank.hip", "jh_longfork.hip", "jh_causal.hip", "jh_api.hip", "jh_multi.hip", "jh_ingest.hip"]
 HOST_SOURCES = ["jh_io.cpp"]
 HEADERS = [os.path.join(CSRC, "jh_internal.h"), os.path.join(ROOT, "include", "jh.h")]
+# headers jh_lin.hip alone includes (csrc/lin/*.h): whatever the directory holds
+LIN_HEADERS = sorted(glob.glob(os.path.join(CSRC, "lin", "*.h")))
 HOST_HEADERS = [os.path.join(ROOT, "include", "jh.h"), os.path.join(ROOT, "include", "jh_io.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
@@ -54,7 +57,7 @@ def build_libjh(verbose=False):
         src = os.path.join(CSRC, s)
         obj = os.path.join(OBJ, s.replace(".hip", ".o"))
         objs.append(obj)
-        if _newer(obj, [src] + HEADERS):
+        if _newer(obj, [src] + HEADERS + (LIN_HEADERS if s == "jh_lin.hip" else [])):
             jobs.append([HIPCC] + HIPFLAGS + ["-c", src, "-o", obj])
     # host-only sources (history ingest, include/jh_io.h): g++, linked into libjh.so
     for s in HOST_SOURCES:

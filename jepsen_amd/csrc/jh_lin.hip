@@ -25,6 +25,7 @@
 #include <hipcub/hipcub.hpp>
 #include <algorithm>
 #include <type_traits>
+#include "lin/lin_common.h"
 
 namespace {
 
@@ -417,8 +418,6 @@ struct DfsArgs {
     // dfs_acc continues it instead of restarting it. null: off.
     int32_t *handoff;
 };
-constexpr int V_HANDED = -9;            // dfs_lean: saved for a takeover, continue from the record
-constexpr int32_t HO_NONE = 0, HO_ASK = 1, HO_DONE = 2, HO_REFUSED = 3, HO_WITHDRAWN = 4, HO_SAVING = 5;
 constexpr int TL_W = 6;         // timeline words per key: BFS, sequential, helper (start, end)
 #ifdef JH_TUNING
 #define TL_REC(tl, key, w) \
@@ -439,7 +438,7 @@ __device__ __forceinline__ bool p1_finished(const int32_t *done, const int32_t *
 // One lane: the key at index idx of a live list, waiting until phase 1 has
 // appended it; -1 once phase 1 has finished without reaching idx. A wait
 // past STREAM_WATCHDOG (a bug, not a slow search: phase 1's longest search
-// is bounded by its quick budget) sets flag 512 and gives up, so the grid
+// is bounded by its quick budget) sets flag 512 (QF_STREAM_WAIT) and gives up, so the grid
 // always drains.
 constexpr unsigned long long STREAM_WATCHDOG = 3000000000ULL;   // 30 s of s_memrealtime (100 MHz)
 __device__ int stream_key(const int32_t *list, const int32_t *live_n, const int32_t *done, const int32_t *tot,
@@ -450,12 +449,12 @@ __device__ int stream_key(const int32_t *list, const int32_t *live_n, const int3
             for (;;) {
                 const int k = ld_agent(&list[idx]);
                 if (k >= 0) return k;
-                if (__builtin_amdgcn_s_memrealtime() - t0 > STREAM_WATCHDOG) { atomicOr(flags, 512); return -1; }
+                if (__builtin_amdgcn_s_memrealtime() - t0 > STREAM_WATCHDOG) { atomicOr(flags, QF_STREAM_WAIT); return -1; }
                 __builtin_amdgcn_s_sleep(2);
             }
         }
         if (p1_finished(done, tot) && idx >= ld_agent(live_n)) return -1;
-        if (__builtin_amdgcn_s_memrealtime() - t0 > STREAM_WATCHDOG) { atomicOr(flags, 512); return -1; }
+        if (__builtin_amdgcn_s_memrealtime() - t0 > STREAM_WATCHDOG) { atomicOr(flags, QF_STREAM_WAIT); return -1; }
         __builtin_amdgcn_s_sleep(20);
     }
 }
@@ -1448,7 +1447,7 @@ __device__ int dfs_search(const DfsArgs &A, const KeyInfo &K, char *tb, int key,
             }
             PROF_MARK(q5); PROF_ADD(pc_pop, q2, q5);
         }
-        if (depth >= A.stack_cap) { verdict = JH_UNKNOWN; if (lane == 0) atomicOr(A.flags, 4); break; }
+        if (depth >= A.stack_cap) { verdict = JH_UNKNOWN; if (lane == 0) atomicOr(A.flags, QF_STACK_OVERFLOW); break; }
     }
     inserts = ins;
     tmax_out = tmax;
@@ -1986,7 +1985,7 @@ done:
             if (lane == 0 && n == nmem) {
                 A.rs_off[key] = (int64_t)off;
                 // Q_RS_N: records published; [91]: takeovers (round 6)
-                atomicAdd((int32_t *)A.rs_used + (ho ? 3 : 2), 1);
+                atomicAdd((int32_t *)A.rs_used + ((ho ? Q_RS_TAKEOVERS : Q_RS_PUBLISHED) - Q_RS_USED), 1);
             }
             if (ho && lane == 0) {
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
@@ -2706,15 +2705,15 @@ __global__ void k_unpack_keys(const uint64_t *__restrict__ in, int n, int32_t *_
 }
 
 // :linear mode has no WGL phase: every key that needs a search goes to the
-// reachable-set analysis, as if phase 1 had handed it on (q[1] all, q[29]
-// LEAN, q[30] WIDE, as phase 1's deferral counters)
+// reachable-set analysis, as if phase 1 had handed it on (Q_DEFER all, Q_DEFER_L
+// LEAN, Q_DEFER_W WIDE, as phase 1's deferral counters)
 __global__ void __launch_bounds__(1024) k_linear_lists(const int32_t *__restrict__ list, const int32_t *n_list,
                                                       const int32_t *__restrict__ list_w, const int32_t *n_list_w,
                                                       int32_t *defer, int32_t *defer_l, int32_t *defer_w, int32_t *q) {
     const int nl = *n_list, nw = *n_list_w;
     for (int i = threadIdx.x; i < nl; i += blockDim.x) { defer[i] = list[i]; defer_l[i] = list[i]; }
     for (int i = threadIdx.x; i < nw; i += blockDim.x) { defer[nl + i] = list_w[i]; defer_w[i] = list_w[i]; }
-    if (threadIdx.x == 0) { q[1] = nl + nw; q[29] = nl; q[30] = nw; }
+    if (threadIdx.x == 0) { q[Q_DEFER] = nl + nw; q[Q_DEFER_L] = nl; q[Q_DEFER_W] = nw; }
 }
 
 // ---------------------------------------------------------------------------
@@ -2947,7 +2946,7 @@ __device__ __forceinline__ bool gset_insert(uint64_t *g, uint32_t gmask, uint64_
                                             int32_t *flags) {
     uint32_t h = (uint32_t)jh_mix64(k) & gmask;
     for (uint32_t n = 0;; n++) {
-        if (n > gmask) { atomicOr(flags, 64); return false; }
+        if (n > gmask) { atomicOr(flags, QF_FULL_SET); return false; }
         const unsigned long long prev = atomicCAS((unsigned long long *)&g[h], 0ULL, (unsigned long long)k);
         if (prev == 0) { slot = h; return true; }
         if (prev == k) return false;
@@ -2995,7 +2994,7 @@ __device__ __forceinline__ void wg_append(WgShared &sh, uint64_t *work, uint32_t
                                           int32_t *flags) {
     const uint32_t pos = atomicAdd(&sh.tail, 1u);
     if (pos < work_cap) __hip_atomic_store(&work[pos], e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    else atomicOr(flags, 64);
+    else atomicOr(flags, QF_FULL_SET);
     if (pos >= sh.cap_total) atomicOr(&sh.status, ENUM_CAP);
 }
 
@@ -3591,7 +3590,7 @@ expand:
             const uint32_t mnew = sh.m_new;
             if (lane == 0) {
                 atomicAdd((unsigned long long *)W.spec_q, (unsigned long long)mnew);
-                atomicAdd(&W.spec_q[2], 1);
+                atomicAdd(&W.spec_q[Q_SPEC_MERGES - Q_SPEC], 1);
             }
             ins += mnew;
             if (ins > budget) { ins = budget; verdict = JH_UNKNOWN; goto done; }
@@ -3688,7 +3687,7 @@ expand:
         }
     }
     if (++n_steps > (1u << 28)) {       // watchdog: far beyond any budget's step count
-        if (lane == 0) atomicOr(A.flags, 128);
+        if (lane == 0) atomicOr(A.flags, QF_STEP_LIMIT);
         verdict = JH_UNKNOWN;
         goto done;
     }
@@ -4128,8 +4127,8 @@ __device__ void spec_enum(const WgArgs &W, WgShared &sh, int lane, char *wtab, u
     const int st = sh.status;
     const int res = st == 0 ? SPEC_DEAD : (st & ENUM_LIVE) ? SPEC_LIVE : SPEC_INC;
     if (lane == 0) {
-        atomicAdd(&W.spec_q[3], 1);
-        if (res == SPEC_DEAD) { S->n = sh.keep_n; S->helper = (int)blockIdx.x; atomicAdd(&W.spec_q[4], 1); }
+        atomicAdd(&W.spec_q[Q_SPEC_JOBS - Q_SPEC], 1);
+        if (res == SPEC_DEAD) { S->n = sh.keep_n; S->helper = (int)blockIdx.x; atomicAdd(&W.spec_q[Q_SPEC_DEAD - Q_SPEC], 1); }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
         int exp = SPEC_CLAIMED;
         if (__hip_atomic_compare_exchange_strong(&S->state, &exp, res, __ATOMIC_RELEASE, __ATOMIC_RELAXED,
@@ -6325,7 +6324,7 @@ __device__ __forceinline__ void xw_waves(const XwArgs &A, size_t wv, unsigned lo
         jh_key_verdict v;
         v.valid = JH_UNKNOWN; v.cause = JH_CAUSE_WINDOW; v.fail_entry = -1; v.explored = 0;
         if (xw_bytes(n_ops, n_ok, sumW) > A.scratch_bytes || (uint32_t)n_ops + 2 > A.stack_cap) {
-            if (lane == 0) { atomicOr(A.flags, 2); A.out[key] = v; }
+            if (lane == 0) { atomicOr(A.flags, QF_TABLE_OVERFLOW); A.out[key] = v; }
             continue;
         }
         const XwTbl T = xw_tbl(tb, n_ops, n_ok, sumW);
@@ -6606,22 +6605,6 @@ static int fit_units(jh_ctx *ctx, int want, uint64_t per_unit, std::initializer_
     return (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)want, fit));
 }
 
-// words of the per-call counter block q (device): queues, list lengths, probe
-// and entry counters of the phases
-constexpr int Q_WORDS = 104;
-constexpr int Q_ENT_ALL = 24, Q_DEFER_L = 29, Q_DEFER_W = 30, Q_DEFER3W = 31;
-constexpr int Q_PROBES_HELP = 32, Q_PROBES_P3 = 34, Q_PROBES_WIDE = 36;
-constexpr int Q_ENT_LEAN = 40, Q_ENT_WIDE = 42, Q_ENT_XW = 44;
-constexpr int Q_T_WIDE = 46;        // [46..47] first WIDE wave start, [48..49] last end (s_memrealtime)
-// the streaming heavy-key pass (round 4): phase 1's finished keys, the LEAN
-// sequential waves of both grids, the BFS's queue, and spans (first key taken,
-// last wave end; s_memrealtime) of the BFS, the LEAN role, the xw role and phase 1
-constexpr int Q_P1_DONE = 64, Q_SEQ_WAVES = 65, Q_BFS_QUEUE = 66;
-constexpr int Q_T_BFS = 68, Q_T_LEAN = 72, Q_T_XW = 76, Q_T_P1 = 80;
-constexpr int Q_ENT_P3 = 84;        // entries of the LEAN keys restarted in phase 3
-constexpr int Q_RS_USED = 88;       // [88..89] resume records' bytes, [90] records published (round 5), [91] takeovers (round 6)
-constexpr int Q_MAINS = 92;         // round 6: late helpers running a key now
-constexpr int Q_SPEC = 96;          // round 6: [96..97] merged nodes, [98] merges, [99] spec jobs, [100] dead results
 // LEAN sequential waves launched with the BFS while phase 1 still runs (the
 // rest start behind phase 1): enough for the keys deferred before it ends
 constexpr int EARLY_LEAN_WAVES = 128;
@@ -6676,24 +6659,216 @@ __global__ void k_req_lists(const int64_t *__restrict__ keys, int n, int64_t K, 
         if (k < 0 || k >= K) continue;
         defer[m] = (int32_t)k; defer_l[m] = (int32_t)k; m++;
     }
-    q[1] = m; q[29] = m; q[30] = 0;
+    q[Q_DEFER] = m; q[Q_DEFER_L] = m; q[Q_DEFER_W] = 0;
 }
 
-void lin_check_independent(jh_ctx *ctx, const jh_history *dh, const jh_lin_opts *opts,
-                           bool keyed, jh_key_verdict *out_dev, jh_summary *sum,
-                           hipStream_t st, const LinCfgReq *cfgreq) {
-    const int64_t n = dh->n;
-    const int64_t K = keyed ? dh->n_keys : 1;
-    if (K >= (1LL << 23)) throw_jh(JH_EUNSUPPORTED, "more than 2^23 keys in one call");
-    if (n >= (1LL << 31)) throw_jh(JH_EUNSUPPORTED, "more than 2^31 entries in one call");
-    const int64_t budget = opts && opts->budget > 0 ? opts->budget : JH_DEFAULT_BUDGET;
-    const int64_t init = opts ? opts->init_value : JH_NIL;
-    const int32_t lflags = opts ? opts->flags : 0;
-    const bool linear_mode = (opts && opts->algorithm == JH_ALGO_LINEAR) || cfgreq;
-    HIP_TRY(hipEventRecord(ctx->ev[0], st));
+namespace {
 
-    // ranges
-    RangeOut *ro = ctx->ws<RangeOut>(WS_MISC, 1);
+// The context's events by their role in a check (the other checkers use the
+// same array with indices of their own)
+enum LinEv {
+    EV_START = 0, EV_P1_START = 1, EV_SEARCHED = 2, EV_END = 3,
+    EV_P1_END = 4, EV_BFS_END = 5, EV_FORK = 6,
+    EV_SEQ_END = 7, EV_XW_START = 8, EV_XW_END = 9, EV_P2_END = 10,
+    EV_WG_START = 11,       // the workgroup-engine tuning mode
+    EV_EARLY_END = 11,      // the streaming pass: its early LEAN grid has ended
+    EV_HELP_END = 12, EV_P3_START = 13,
+};
+
+// The stable partition of a history's rows by key: (key, row) pairs, radix
+// sort, CSR segment offsets (k_seg_off also leaves the longest segment in ro).
+// The check and key_index both start with it. Each caller allocates in its
+// own order (on a cold context that is the order of the hipMallocs): the four
+// pair buffers by partition_buffers; the offsets by the caller beforehand
+// (key_index), or here after the sort's temporary when p.off is null (the check).
+struct KeyPartition {
+    uint32_t *kA, *kB, *rA, *rB;    // (key, row) pairs, n each: as read (A), sorted (B)
+    uint32_t *off;                  // segment offsets (K + 2)
+};
+KeyPartition partition_buffers(jh_ctx *ctx, int64_t n) {
+    KeyPartition p{};
+    p.kA = ctx->ws<uint32_t>(WS_KEYS_A, n); p.kB = ctx->ws<uint32_t>(WS_KEYS_B, n);
+    p.rA = ctx->ws<uint32_t>(WS_ROWS_A, n); p.rB = ctx->ws<uint32_t>(WS_ROWS_B, n);
+    return p;
+}
+void partition_by_key(jh_ctx *ctx, KeyPartition &p, const int64_t *key, int64_t n, int64_t K, bool keyed,
+                      RangeOut *ro, hipStream_t st) {
+    if (n > 0)
+        k_keys<<<grid_for(n, 256), 256, 0, st>>>(keyed ? key : nullptr, n, K, keyed ? 1 : 0, p.kA, p.rA);
+    const int endbit = bits_for((uint64_t)K);
+    size_t tb = 0;
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, p.kA, p.kB, p.rA, p.rB, (int)n, 0, endbit, st));
+    void *tmp = ctx->ws<char>(WS_SORT_TMP, tb);
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, tb, p.kA, p.kB, p.rA, p.rB, (int)n, 0, endbit, st));
+    if (!p.off) p.off = ctx->ws<uint32_t>(WS_SEG_OFF, K + 2);
+    k_seg_off<<<grid_for(K + 1, 256), 256, 0, st>>>(p.kB, n, K, p.off, ro);
+}
+
+// table sizes of the reachable-set engine for up to reach_cap configurations of a key
+struct BfsSizes {
+    uint32_t set_cap, q_cap;
+};
+BfsSizes bfs_table_sizes(int64_t reach_cap) {
+    uint32_t set_cap = 1u << 12;
+    while ((int64_t)set_cap < 2 * reach_cap && set_cap < (1u << 30)) set_cap <<= 1;
+    const uint32_t q_cap = (uint32_t)std::min<int64_t>(reach_cap + 64, (int64_t)1 << 30);
+    return BfsSizes{set_cap, q_cap};
+}
+
+// One call of lin_check_independent: what its steps share. The functions
+// below are the steps, in the order the call runs them; each one's sequence
+// of allocations (ctx->ws), fit_units queries, memsets and event records is
+// part of the schedule it belongs to (an allocation synchronises, and
+// fit_units counts what is already held), so statements do not move between
+// them freely.
+struct LinRun {
+    // ---- the call
+    jh_ctx *ctx = nullptr;
+    const jh_history *dh = nullptr;
+    const jh_lin_opts *opts = nullptr;
+    bool keyed = false;
+    jh_key_verdict *out_dev = nullptr;
+    jh_summary *sum = nullptr;
+    hipStream_t st = nullptr;
+    const LinCfgReq *cfgreq = nullptr;
+    int64_t n = 0, K = 0, budget = 0, init = 0;
+    int32_t lflags = 0;
+    bool linear_mode = false;
+
+    // ---- the prepared history (prepare)
+    RangeOut *ro = nullptr;
+    long long vmin = 0, vmax = 0, n_states = 0;
+    bool per_key_values = false;
+    int init_state = 0;
+    uint32_t *kB = nullptr, *rB = nullptr, *off = nullptr;   // sorted keys, their rows, segment offsets
+    int64_t m = 0;                  // keyed rows
+    int smax = 1;                   // longest key segment
+    Rec *rec = nullptr;
+    int32_t *pair = nullptr;
+    unsigned long long *viol = nullptr;
+    int32_t *rank = nullptr;
+
+    // ---- memo generations (memo_generation)
+    uint32_t gen_span = 0;
+    bool clear_memo = false;
+
+    // ---- the counter block, the lists and phase 1 (phase1_tables, phase1_args, phase1_resume)
+    const uint32_t memo_cap1 = 1u << 16;    // phase 1's HBM memo, entries per wave
+    int64_t quick = 0;
+    int waves1 = 0;
+    uint32_t stack_cap = 0;
+    uint64_t scr_bytes = 0, scr_bytes_h = 0, scr_bytes_bfs = 0;
+    uint64_t *memo = nullptr;
+    Frame *stack = nullptr;
+    char *scr = nullptr;
+    int32_t *q = nullptr;           // the counter block (the Q_* words above)
+    int32_t qh[Q_WORDS];            // its host copy
+    int32_t *list = nullptr, *list1 = nullptr, *list_w = nullptr, *list_x = nullptr;
+    int32_t *defer = nullptr, *defer_l = nullptr, *defer_w = nullptr;
+    uint64_t *d64 = nullptr;
+    KeyMeta *meta = nullptr;
+    char *arena = nullptr;
+    DfsArgs a{};                    // phase 1; the heavy-key searches start from a copy
+    const char *dbgenv = nullptr;
+    bool dbg2 = false, defer_times = false;
+    unsigned long long *dbg = nullptr;
+    bool skip_p1 = false, p1_only = false, resume = false;
+
+    // ---- the heavy keys: counts, budgets, the engines' arguments, wave counts
+    int n_defer = 0, n_def_l = 0, n_def_w = 0, n_x = 0;
+    int waves_x = 0;
+    XwArgs xa{};
+    int64_t p2 = 0;
+    uint32_t cap2 = 0;
+    int32_t *defer3 = nullptr, *defer3w = nullptr;
+    int32_t *claim = nullptr;
+    int waves_w = 0, waves2 = 0;
+    int waves3 = 0;                  // phase 3's LEAN waves (full tables; waves2 unless p2_small)
+    uint32_t cap2l = 0;              // phase 2's LEAN tables (entries per wave)
+    bool p2_small_ok = true;         // (the streaming pass keeps round 4's sizing)
+    bool split3 = false, split3w = false;
+    DfsArgs bw{};                    // the WIDE keys' sequential search
+    unsigned long long *acc_stats = nullptr;
+    int n_wg = 0;
+    int n_unres = 0;
+    bool use_wg = false, wg_race = false, stream_p2 = false;
+    int wg2 = 0, n_help = 0;
+    BfsArgs c{};                     // the BFS
+    DfsArgs b{};                     // the LEAN keys' sequential search
+    WgArgs wr{}, wh{};               // the workgroup race (JH_WG=2), the late helpers
+    unsigned long long *seq_start = nullptr;
+    uint32_t *seq_stall = nullptr;
+    int p2_per_cu = P2_LEAN_PER_CU;
+    bool p2_m = true, bfs_only = false;
+
+    KeySrc key_src() const { return KeySrc{rec, pair, off, rB, viol, rank, q + Q_FLAGS}; }
+
+    // preparation
+    void prepare();
+    void prep_ranges();
+    void prep_records();
+    void intern_per_key();
+    void memo_generation();
+    // phase 1
+    void phase1_tables();
+    void phase1_args();
+    void phase1_resume();
+    void phase2_budgets();
+    // the engines' arguments and tables
+    void ensure_lds_attrs();
+    void prep_xw(const int32_t *qw);
+    void prep_wide();
+    void launch_wide(hipStream_t sw, bool p2);
+    WgArgs build_wg(int wg_cus, int32_t *wg_claim, int32_t *wg_queue, bool all_cus = false);
+    void prep_race(int nd_all, int nd_l);
+    void race_bfs(int nd_all);
+    int race_helper_count(int nd_l);
+    uint64_t *race_lean_sizing(int nd_l, int help_cus);
+    void race_helpers(int nd_l);
+    void race_lean_args(int nd_l, uint64_t *memo2);
+    void timeline_tables(bool wide);
+    DfsArgs phase1_wide_args() const;
+    DfsArgs phase3_lean_args() const;
+    DfsArgs phase3_wide_args() const;
+    void launch_phase3_lean(int waves, hipStream_t s);
+    void entry_lists(bool live);
+    void record_no_heavy_keys();
+    // the schedules
+    void run_streaming();
+    void run_phase1();
+    void sort_deferred();
+    void run_stage1();
+    void launch_xw();
+    void run_wg_mode();
+    void run_linear();
+    void run_race();
+    // results
+    void finish();
+    void fill_summary(const long long *sh);
+    // tuning builds (lin_diag.h)
+    void diag_phase1_waves();
+    void diag_helper_keys();
+    void diag_bfs_dump();
+    void diag_race_waves();
+    void diag_defer_timeline();
+    void diag_acc_trace();
+    void diag_ws_report();
+    void diag_xw_prof();
+    void diag_summary();
+};
+
+}  // namespace
+
+#include "lin/lin_diag.h"
+
+namespace {
+
+// ---------------------------------------------------------------------------
+// Preparation: value and process ranges, the partition by key, records,
+// pairing, and (for wide value ranges) per-key interning.
+// writes: ro, vmin, vmax, per_key_values, init_state, n_states
+void LinRun::prep_ranges() {
+    ro = ctx->ws<RangeOut>(WS_MISC, 1);
     RangeOut ro_init{LLONG_MAX, LLONG_MIN, -1, 0, 0, 0, 0};
     HIP_TRY(hipMemcpyAsync(ro, &ro_init, sizeof ro_init, hipMemcpyHostToDevice, st));
     if (n > 0)
@@ -6705,39 +6880,23 @@ void lin_check_independent(jh_ctx *ctx, const jh_history *dh, const jh_lin_opts 
     if (keyed && rh.unkeyed_client)
         throw_jh(JH_EUNSUPPORTED, "client ops whose :value is not an independent tuple");
     if (rh.pmax > INT32_MAX) throw_jh(JH_EUNSUPPORTED, "process ids beyond int32");
-    long long vmin = rh.vmin, vmax = rh.vmax;
+    vmin = rh.vmin; vmax = rh.vmax;
     if (init != JH_NIL) { vmin = std::min<long long>(vmin, init); vmax = std::max<long long>(vmax, init); }
     if (vmin > vmax) { vmin = 0; vmax = 0; }
     // values spanning more than one 16-bit state range are interned per key
     // (k_ival..k_iassign) instead of as one global offset
-    const bool per_key_values = (unsigned long long)(vmax - vmin) >= (unsigned long long)(RQ_EMPTY - 3) ||
-                                (lflags & JH_LIN_INTERN_PER_KEY) != 0;
-    const int init_state = init == JH_NIL ? 0 : per_key_values ? 1 : (int)(init - vmin + 1);
-    long long n_states = vmax - vmin + 2;      // state ids 0 (nil) .. vmax - vmin + 1
+    per_key_values = (unsigned long long)(vmax - vmin) >= (unsigned long long)(RQ_EMPTY - 3) ||
+                     (lflags & JH_LIN_INTERN_PER_KEY) != 0;
+    init_state = init == JH_NIL ? 0 : per_key_values ? 1 : (int)(init - vmin + 1);
+    n_states = vmax - vmin + 2;      // state ids 0 (nil) .. vmax - vmin + 1
+}
 
-    // partition by key
-    uint32_t *kA = ctx->ws<uint32_t>(WS_KEYS_A, n), *kB = ctx->ws<uint32_t>(WS_KEYS_B, n);
-    uint32_t *rA = ctx->ws<uint32_t>(WS_ROWS_A, n), *rB = ctx->ws<uint32_t>(WS_ROWS_B, n);
-    if (n > 0)
-        k_keys<<<grid_for(n, 256), 256, 0, st>>>(keyed ? dh->key : nullptr, n, K, keyed ? 1 : 0, kA, rA);
-    const int endbit = bits_for((uint64_t)K);
-    size_t tb = 0;
-    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, kA, kB, rA, rB, (int)n, 0, endbit, st));
-    void *tmp = ctx->ws<char>(WS_SORT_TMP, tb);
-    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, tb, kA, kB, rA, rB, (int)n, 0, endbit, st));
-    uint32_t *off = ctx->ws<uint32_t>(WS_SEG_OFF, K + 2);
-    k_seg_off<<<grid_for(K + 1, 256), 256, 0, st>>>(kB, n, K, off, ro);
-    uint32_t m_keyed = 0;
-    HIP_TRY(hipMemcpyAsync(&m_keyed, off + K, sizeof m_keyed, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(&rh, ro, sizeof rh, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    const int64_t m = m_keyed;
-    const int smax = std::max(rh.smax, 1);
-
-    Rec *rec = ctx->ws<Rec>(WS_REC, m);
-    int32_t *pair = ctx->ws<int32_t>(WS_PAIR, m);
-    unsigned long long *viol = ctx->ws<unsigned long long>(WS_VIOL, K);
-    int32_t *rank = ctx->ws<int32_t>(WS_RANK, m);
+// writes: rec, pair, viol, rank
+void LinRun::prep_records() {
+    rec = ctx->ws<Rec>(WS_REC, m);
+    pair = ctx->ws<int32_t>(WS_PAIR, m);
+    viol = ctx->ws<unsigned long long>(WS_VIOL, K);
+    rank = ctx->ws<int32_t>(WS_RANK, m);
     HIP_TRY(hipMemsetAsync(viol, 0xFF, sizeof(unsigned long long) * K, st));
     if (m > 0) {
         HIP_TRY(hipMemsetAsync(pair, 0xFF, sizeof(int32_t) * m, st));
@@ -6746,45 +6905,69 @@ void lin_check_independent(jh_ctx *ctx, const jh_history *dh, const jh_lin_opts 
         k_pair<<<grid_for((m + 63) / 64, 4, 16384), 256, 0, st>>>(rec, kB, off, m, pair, viol);
         k_orphan<<<grid_for(m, 256), 256, 0, st>>>(rec, kB, m, pair, viol);
     }
-    if (per_key_values && m > 0) {
-        const int64_t n2 = 2 * m;
-        if (n2 >= (1LL << 32) - 1) throw_jh(JH_EUNSUPPORTED, "too many entries for per-key value interning");
-        uint64_t *iu = ctx->ws<uint64_t>(WS_IV_U, 2 * n2);
-        uint32_t *ix = ctx->ws<uint32_t>(WS_IV_IDX, 3 * n2);
-        uint32_t *ik = ctx->ws<uint32_t>(WS_IV_KEY, 2 * n2);
-        uint32_t *rinit = ctx->ws<uint32_t>(WS_IV_RINIT, K + 1);
-        unsigned int *maxid = (unsigned int *)ctx->ws<uint32_t>(WS_IV_MAX, 4);
-        uint32_t *flag = ik + n2;                   // reuses the key buffer's second half
-        k_ival<<<grid_for(n2, 256), 256, 0, st>>>(dh->value, dh->value2, dh->f, rB, m, iu, ix);
-        size_t tb1 = 0, tb2 = 0, tb3 = 0;
-        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb1, iu, iu + n2, ix, ix + n2, (int)n2, 0, 64, st));
-        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb2, ik, ik + n2, ix + n2, ix + 2 * n2, (int)n2, 0, endbit, st));
-        HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, tb3, flag, flag, (int)n2, st));
-        char *itmp = ctx->ws<char>(WS_IV_TMP, std::max(tb1, std::max(tb2, tb3)));
-        // by value (iu keeps the original values, iu + n2 the sorted ones) ...
-        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(itmp, tb1, iu, iu + n2, ix, ix + n2, (int)n2, 0, 64, st));
-        // ... then stably by key: each key's items in value order
-        k_ikey<<<grid_for(n2, 256), 256, 0, st>>>(ix + n2, kB, n2, ik);
-        uint32_t *ik2 = (uint32_t *)(iu + n2);      // sorted values no longer needed: key output
-        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(itmp, tb2, ik, ik2, ix + n2, ix + 2 * n2, (int)n2, 0, endbit, st));
-        const uint32_t *idx2 = ix + 2 * n2;
-        k_iflag<<<grid_for(n2, 256), 256, 0, st>>>(idx2, iu, kB, off, n2, flag);
-        HIP_TRY(hipcub::DeviceScan::InclusiveSum(itmp, tb3, flag, flag, (int)n2, st));
-        const uint64_t init_u = (uint64_t)init ^ (1ULL << 63);
-        HIP_TRY(hipMemsetAsync(rinit, 0, sizeof(uint32_t) * (K + 1), st));
-        HIP_TRY(hipMemsetAsync(maxid, 0, sizeof(unsigned int), st));
-        if (init != JH_NIL) k_iinit<<<grid_for(n2, 256), 256, 0, st>>>(idx2, iu, kB, off, flag, n2, init_u, rinit);
-        k_iassign<<<grid_for(n2, 256), 256, 0, st>>>(idx2, iu, kB, off, flag, n2, init != JH_NIL ? 1 : 0, init_u,
-                                                     rinit, rec, viol, maxid);
-        unsigned int mh = 0;
-        HIP_TRY(hipMemcpyAsync(&mh, maxid, sizeof mh, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        n_states = (long long)std::max<unsigned int>(mh, init != JH_NIL ? 1u : 0u) + 1;
-    }
+}
 
-    // memo generation tags: distinct per (call, key, pass); wrap -> clear
-    const uint32_t gen_span = (uint32_t)(3 * K + 3);
-    bool clear_memo = false;
+// per-key dense interning of the values (k_ival .. k_iassign); sets n_states
+// writes: n_states (and the records' value ids, on the device)
+void LinRun::intern_per_key() {
+    const int64_t n2 = 2 * m;
+    if (n2 >= (1LL << 32) - 1) throw_jh(JH_EUNSUPPORTED, "too many entries for per-key value interning");
+    const int endbit = bits_for((uint64_t)K);
+    uint64_t *iu = ctx->ws<uint64_t>(WS_IV_U, 2 * n2);
+    uint32_t *ix = ctx->ws<uint32_t>(WS_IV_IDX, 3 * n2);
+    uint32_t *ik = ctx->ws<uint32_t>(WS_IV_KEY, 2 * n2);
+    uint32_t *rinit = ctx->ws<uint32_t>(WS_IV_RINIT, K + 1);
+    unsigned int *maxid = (unsigned int *)ctx->ws<uint32_t>(WS_IV_MAX, 4);
+    uint32_t *flag = ik + n2;                   // reuses the key buffer's second half
+    k_ival<<<grid_for(n2, 256), 256, 0, st>>>(dh->value, dh->value2, dh->f, rB, m, iu, ix);
+    size_t tb1 = 0, tb2 = 0, tb3 = 0;
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb1, iu, iu + n2, ix, ix + n2, (int)n2, 0, 64, st));
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb2, ik, ik + n2, ix + n2, ix + 2 * n2, (int)n2, 0, endbit, st));
+    HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, tb3, flag, flag, (int)n2, st));
+    char *itmp = ctx->ws<char>(WS_IV_TMP, std::max(tb1, std::max(tb2, tb3)));
+    // by value (iu keeps the original values, iu + n2 the sorted ones) ...
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(itmp, tb1, iu, iu + n2, ix, ix + n2, (int)n2, 0, 64, st));
+    // ... then stably by key: each key's items in value order
+    k_ikey<<<grid_for(n2, 256), 256, 0, st>>>(ix + n2, kB, n2, ik);
+    uint32_t *ik2 = (uint32_t *)(iu + n2);      // sorted values no longer needed: key output
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(itmp, tb2, ik, ik2, ix + n2, ix + 2 * n2, (int)n2, 0, endbit, st));
+    const uint32_t *idx2 = ix + 2 * n2;
+    k_iflag<<<grid_for(n2, 256), 256, 0, st>>>(idx2, iu, kB, off, n2, flag);
+    HIP_TRY(hipcub::DeviceScan::InclusiveSum(itmp, tb3, flag, flag, (int)n2, st));
+    const uint64_t init_u = (uint64_t)init ^ (1ULL << 63);
+    HIP_TRY(hipMemsetAsync(rinit, 0, sizeof(uint32_t) * (K + 1), st));
+    HIP_TRY(hipMemsetAsync(maxid, 0, sizeof(unsigned int), st));
+    if (init != JH_NIL) k_iinit<<<grid_for(n2, 256), 256, 0, st>>>(idx2, iu, kB, off, flag, n2, init_u, rinit);
+    k_iassign<<<grid_for(n2, 256), 256, 0, st>>>(idx2, iu, kB, off, flag, n2, init != JH_NIL ? 1 : 0, init_u,
+                                                 rinit, rec, viol, maxid);
+    unsigned int mh = 0;
+    HIP_TRY(hipMemcpyAsync(&mh, maxid, sizeof mh, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    n_states = (long long)std::max<unsigned int>(mh, init != JH_NIL ? 1u : 0u) + 1;
+}
+
+// writes: kB, rB, off, m, smax, and what its three steps write
+void LinRun::prepare() {
+    prep_ranges();
+    KeyPartition kp = partition_buffers(ctx, n);
+    partition_by_key(ctx, kp, dh->key, n, K, keyed, ro, st);
+    kB = kp.kB; rB = kp.rB; off = kp.off;
+    uint32_t m_keyed = 0;
+    RangeOut rh;
+    HIP_TRY(hipMemcpyAsync(&m_keyed, off + K, sizeof m_keyed, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&rh, ro, sizeof rh, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    m = m_keyed;
+    smax = std::max(rh.smax, 1);
+    prep_records();
+    if (per_key_values && m > 0) intern_per_key();
+}
+
+// memo generation tags: distinct per (call, key, pass); wrap -> clear
+// writes: gen_span, clear_memo, ctx->gen_base
+void LinRun::memo_generation() {
+    gen_span = (uint32_t)(3 * K + 3);
+    clear_memo = false;
     // JH_LIN_GEN_JUMP (tests): start this call at the top of the generation range,
     // so it wraps and must clear every memo table before its searches read them
     if (lflags & JH_LIN_GEN_JUMP) ctx->gen_base = (1u << GEN_BITS) - 2;
@@ -6794,89 +6977,98 @@ void lin_check_independent(jh_ctx *ctx, const jh_history *dh, const jh_lin_opts 
         clear_memo = true;
 #endif
     }
+}
 
-    // phase 1: every key, quick budget, persistent grid
-    const uint32_t memo_cap1 = 1u << 16;
+// ---------------------------------------------------------------------------
+// Phase 1: every key, quick budget, persistent grid.
+// Its waves' tables, the counter block, the lists, and every key's search
+// tables (k_key_tables; <= 8 B per entry + 32 B per key)
+// writes: quick, waves1, memo, stack, stack_cap, scr, scr_bytes*, q, list, list1, list_w, list_x, defer*, d64, meta, arena
+void LinRun::phase1_tables() {
     // 8192: measured against 4096 (C3 rank 0 50.7 -> 42.4 ms, C4 635 -> 430 ms, C5 and ranks 3/4/6
     // unchanged): phase 1 runs 15 waves per CU, phase 2 one, and phase 2 restarts a deferred
     // key from scratch, so every key phase 1 can finish is cheaper there
-    int64_t quick = std::min<int64_t>(budget, QUICK_BUDGET);
+    quick = std::min<int64_t>(budget, QUICK_BUDGET);
     if (opts && opts->quick_budget > 0)
         quick = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(budget, memo_cap1 / 2), opts->quick_budget));
     int p1_per_cu = 163840 / MemoQ::LDS;
     if (opts && opts->p1_waves_per_cu > 0) p1_per_cu = std::min(p1_per_cu, (int)opts->p1_waves_per_cu);
-    const int waves1 = (int)std::min<int64_t>(K, (int64_t)ctx->n_cu * p1_per_cu);
-    uint64_t *memo = ctx->ws<uint64_t>(WS_MEMO, (size_t)waves1 * memo_cap1 * 2, /*zero=*/true);
+    waves1 = (int)std::min<int64_t>(K, (int64_t)ctx->n_cu * p1_per_cu);
+    memo = ctx->ws<uint64_t>(WS_MEMO, (size_t)waves1 * memo_cap1 * 2, /*zero=*/true);
     if (clear_memo) HIP_TRY(hipMemsetAsync(memo, 0, ctx->bufs[WS_MEMO].bytes, st));
-    const uint32_t stack_cap = (uint32_t)smax + 2;
-    Frame *stack = ctx->ws<Frame>(WS_STACK, (size_t)waves1 * stack_cap);
-    const uint64_t scr_bytes = MemoQ::SLOTS * 8;          // per wave: the memo eviction stage
-    const uint64_t scr_bytes_h = MemoH::SLOTS * 8;
-    const uint64_t scr_bytes_bfs = (((uint64_t)smax * 84 + 4096) + 255) & ~255ULL;
-    char *scr = ctx->ws<char>(WS_SCRATCH, (size_t)waves1 * scr_bytes);
-    int32_t *q = ctx->ws<int32_t>(WS_QUEUE, Q_WORDS);
-    int32_t *list = ctx->ws<int32_t>(WS_STATS, K);
+    stack_cap = (uint32_t)smax + 2;
+    stack = ctx->ws<Frame>(WS_STACK, (size_t)waves1 * stack_cap);
+    scr_bytes = MemoQ::SLOTS * 8;          // per wave: the memo eviction stage
+    scr_bytes_h = MemoH::SLOTS * 8;
+    scr_bytes_bfs = (((uint64_t)smax * 84 + 4096) + 255) & ~255ULL;
+    scr = ctx->ws<char>(WS_SCRATCH, (size_t)waves1 * scr_bytes);
+    q = ctx->ws<int32_t>(WS_QUEUE, Q_WORDS);
+    list = ctx->ws<int32_t>(WS_STATS, K);
     // the deferred keys, ordered for the heavy pass (k_sort_defer): every one
     // (the BFS's list), the LEAN ones and the WIDE ones (each mode's own searches)
-    int32_t *defer = ctx->ws<int32_t>(WS_DEFER, 3 * (size_t)(K + 1));
-    int32_t *defer_l = defer + (K + 1), *defer_w = defer + 2 * (K + 1);
-    uint64_t *d64 = ctx->ws<uint64_t>(WS_DEFER64, 3 * (size_t)(K + 1));
-    unsigned long long *probes = (unsigned long long *)(q + 4);
+    defer = ctx->ws<int32_t>(WS_DEFER, 3 * (size_t)(K + 1));
+    defer_l = defer + (K + 1); defer_w = defer + 2 * (K + 1);
+    d64 = ctx->ws<uint64_t>(WS_DEFER64, 3 * (size_t)(K + 1));
     HIP_TRY(hipMemsetAsync(q, 0, Q_WORDS * sizeof(int32_t), st));
     HIP_TRY(hipMemsetAsync(q + Q_T_WIDE, 0xFF, 2 * sizeof(int32_t), st));
     for (int w : {Q_T_BFS, Q_T_LEAN, Q_T_XW, Q_T_P1}) HIP_TRY(hipMemsetAsync(q + w, 0xFF, 2 * sizeof(int32_t), st));
 
-    // per-key search tables for every key (<= 8 B per entry + 32 B per key)
-    KeyMeta *meta = ctx->ws<KeyMeta>(WS_META, K);
-    char *arena = ctx->ws<char>(WS_ARENA, (size_t)m * 8 + (size_t)K * 32 + 256);
+    meta = ctx->ws<KeyMeta>(WS_META, K);
+    arena = ctx->ws<char>(WS_ARENA, (size_t)m * 8 + (size_t)K * 32 + 256);
     TblArgs ta{};
-    ta.src = KeySrc{rec, pair, off, rB, viol, rank, q + 2};
-    ta.K = K; ta.meta = meta; ta.arena = arena; ta.bump = (unsigned long long *)(q + 10);
-    int32_t *list_w = ctx->ws<int32_t>(WS_LIST_W, K);
-    ta.out = out_dev; ta.list = list; ta.n_list = q + 12; ta.list_w = list_w; ta.n_list_w = q + 13;
-    int32_t *list_x = ctx->ws<int32_t>(WS_LIST_X, K);
-    ta.list_x = list_x; ta.n_list_x = q + 19; ta.xw_max = (unsigned long long *)(q + 26);
+    ta.src = key_src();
+    ta.K = K; ta.meta = meta; ta.arena = arena; ta.bump = (unsigned long long *)(q + Q_BUMP);
+    list_w = ctx->ws<int32_t>(WS_LIST_W, K);
+    ta.out = out_dev; ta.list = list; ta.n_list = q + Q_N_LIST; ta.list_w = list_w; ta.n_list_w = q + Q_N_LIST_W;
+    list_x = ctx->ws<int32_t>(WS_LIST_X, K);
+    ta.list_x = list_x; ta.n_list_x = q + Q_N_LIST_X; ta.xw_max = (unsigned long long *)(q + Q_XW_MAX);
     ta.states8 = n_states <= 256 ? 1 : 0;
     k_key_tables<<<(unsigned)std::min<int64_t>((K + 3) / 4, 8192), 256, 0, st>>>(ta);
 
-    int32_t *list1 = list;
+    // phase 1 takes its LEAN keys costliest first
+    list1 = list;
     if (!tune_env("JH_NO_LPT") && K > 1) {
         uint32_t *cost = ctx->ws<uint32_t>(WS_LCOST, 2 * K);
         int32_t *lv = ctx->ws<int32_t>(WS_LSORT, 2 * K);
-        k_list_cost<<<grid_for(K, 256, 4096), 256, 0, st>>>(list, q + 12, meta, K, cost, lv);
+        k_list_cost<<<grid_for(K, 256, 4096), 256, 0, st>>>(list, q + Q_N_LIST, meta, K, cost, lv);
         size_t tbl = 0;
         HIP_TRY(hipcub::DeviceRadixSort::SortPairsDescending(nullptr, tbl, cost, cost + K, lv, lv + K, (int)K, 0, 32, st));
         HIP_TRY(hipcub::DeviceRadixSort::SortPairsDescending(ctx->ws<char>(WS_LTMP, tbl), tbl, cost, cost + K, lv,
                                                              lv + K, (int)K, 0, 32, st));
         list1 = lv + K;
     }
+}
 
-    DfsArgs a{};
+// phase 1's arguments, and the tuning builds' debug and timeline buffers
+// writes: a, dbgenv, dbg2, dbg, defer_times
+void LinRun::phase1_args() {
+    a = DfsArgs{};
     a.rec = rec; a.pair = pair; a.off = off; a.rows = rB; a.viol = viol; a.rank = rank;
-    a.list = list1; a.n_list = 0; a.n_list_dev = q + 12; a.queue = q; a.out = out_dev;
+    a.list = list1; a.n_list = 0; a.n_list_dev = q + Q_N_LIST; a.queue = q + Q_QUEUE; a.out = out_dev;
     a.meta = meta; a.tables = arena;
-    a.defer_list = nullptr; a.defer_count = q + 1;
+    a.defer_list = nullptr; a.defer_count = q + Q_DEFER;
     a.defer64 = d64; a.defer_kind = d64 + (K + 1); a.defer_kind_count = q + Q_DEFER_L;
     a.memo = memo; a.memo_cap = memo_cap1; a.stack = stack; a.stack_cap = stack_cap;
     a.scratch = scr; a.scratch_bytes = scr_bytes; a.budget = quick; a.defer = quick < budget ? 1 : 0;
-    a.init_state = init_state; a.gen_base = ctx->gen_base; a.flags = q + 2; a.probes = probes;
+    a.init_state = init_state; a.gen_base = ctx->gen_base; a.flags = q + Q_FLAGS;
+    a.probes = (unsigned long long *)(q + Q_PROBES_P1);
     a.states8 = n_states <= 256 ? 1 : 0;
-    // (the default, HANDOVER_MIN, only once resume is known to be on: below)
+    // (the default, HANDOVER_MIN, only once resume is known to be on: phase1_resume)
     a.handover_min = 0;
     if (a.defer && !(lflags & JH_LIN_NO_HANDOVER) && opts && opts->handover_min)
         a.handover_min = std::max(0, opts->handover_min);
     if (const char *e = tune_env("JH_HANDOVER_MIN")) a.handover_min = a.defer ? std::max(0, atoi(e)) : 0;
     a.prio_ins = P1_PRIO_INS;
     if (const char *e = tune_env("JH_P1_PRIO")) a.prio_ins = std::max(0, atoi(e));
-    const char *dbgenv = tune_env("JH_DEBUG");
-    const bool dbg2 = dbgenv && atoi(dbgenv) >= 2;
-    unsigned long long *dbg = nullptr;
+    dbgenv = tune_env("JH_DEBUG");
+    dbg2 = dbgenv && atoi(dbgenv) >= 2;
+    dbg = nullptr;
     if (dbg2) {
         dbg = ctx->ws<unsigned long long>(WS_DEBUG, (size_t)(waves1 + 512) * 16);
         HIP_TRY(hipMemsetAsync(dbg, 0, sizeof(unsigned long long) * (waves1 + 512) * 16, st));
         a.dbg = dbg;
     }
-    const bool defer_times = tune_env("JH_DEFER_TIMES") && atoi(tune_env("JH_DEFER_TIMES"));
+    defer_times = tune_env("JH_DEFER_TIMES") && atoi(tune_env("JH_DEFER_TIMES"));
     if (defer_times) {
         a.defer_time = ctx->ws<unsigned long long>(WS_DEFER_TIME, (size_t)K + 2);
         HIP_TRY(hipMemsetAsync(a.defer_time, 0, sizeof(unsigned long long) * (K + 2), st));
@@ -6884,1098 +7076,1003 @@ void lin_check_independent(jh_ctx *ctx, const jh_history *dh, const jh_lin_opts 
         a.defer_info = ctx->ws<unsigned long long>(WS_DEFER_INFO, 2 * (size_t)K);
         HIP_TRY(hipMemsetAsync(a.defer_info, 0, sizeof(unsigned long long) * 2 * K, st));
     }
-    const bool skip_p1 = (lflags & JH_LIN_SKIP_PHASE1) != 0 && !linear_mode;
-    const bool p1_only = (lflags & JH_LIN_PHASE1_ONLY) != 0 && !linear_mode && !skip_p1;
-    // resume (round 5): phase 1's deferred LEAN searches saved for the heavy-key
-    // pass (a record is <= 64 B + a frame per stack level + 16 B per insert)
-    // (not for the workgroup engine's tuning modes, JH_WG: its
-    // searches start at the root, so records would only be written)
-    const bool wg_mode = tune_env("JH_WG") && atoi(tune_env("JH_WG")) != 0;
-    const bool resume = a.defer && !linear_mode && !skip_p1 && !p1_only && !(lflags & JH_LIN_NO_RESUME) &&
-                        !(lflags & JH_LIN_STREAM) && !wg_mode &&
-                        !tune_env("JH_NO_RESUME");
-    if (resume) {
-        if (!ctx->hbm_total) {
-            size_t fr = 0, tot = 0;
-            HIP_TRY(hipMemGetInfo(&fr, &tot));
-            ctx->hbm_total = tot;
-        }
-        // ADVICE r5 / VERDICT r5 item 7: the record arena and the slot log are
-        // bounded by the device's HBM over the contexts sharing it (1/64 each:
-        // 4.5 GB for one context on an MI355X, so the 256 MB cap rules there).
-        // A smaller log only fails saves (those searches restart: same results)
-        const uint64_t rs_lim = (uint64_t)ctx->hbm_total /
-                                (64 * (uint64_t)std::max(ctx->share, device_open_contexts(ctx->device)));
-        const uint64_t per_key = 64 + (uint64_t)stack_cap * sizeof(Frame) + (uint64_t)quick * 16;
-        // (+ 64 MB for the takeovers' records, round 6)
-        const uint64_t cap = std::min<uint64_t>(std::min<uint64_t>((uint64_t)320 << 20, rs_lim),
-                                                (uint64_t)K * per_key + ((uint64_t)64 << 20));
-        a.rs_arena = ctx->ws<uint8_t>(WS_RS_ARENA, cap);
-        a.rs_cap = cap;
-        a.rs_off = ctx->ws<int64_t>(WS_RS_OFF, K);
-        a.rs_used = (unsigned long long *)(q + Q_RS_USED);
-        HIP_TRY(hipMemsetAsync(a.rs_off, 0xFF, (size_t)K * sizeof(int64_t), st));
-        a.rs_mode = 1;
-#ifdef JH_DUP_WRITE
-        {
-            ulonglong2 *mirror = ctx->ws<ulonglong2>(WS_DEFER_INFO + 1, (size_t)1 << 26);
-            HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_dup_base), &mirror, sizeof mirror));
-        }
-#endif
-        if (!tune_env("JH_RS_SCAN")) {
-            a.hlog_cap = (uint32_t)std::min<int64_t>(std::max<int64_t>(quick, 1024), 32768);
-            a.hlog_cap = (uint32_t)std::max<uint64_t>(256, std::min<uint64_t>(a.hlog_cap, rs_lim / (4 * (uint64_t)std::max(1, waves1))));
-            a.hlog = ctx->ws<uint32_t>(WS_RS_LOG, (size_t)waves1 * a.hlog_cap);
-        }
-        // a handed-over search continues where it stopped: the hand-over is free
-        if (!(lflags & JH_LIN_NO_HANDOVER) && !(opts && opts->handover_min) && !tune_env("JH_HANDOVER_MIN"))
-            a.handover_min = HANDOVER_MIN;
-    }
-    int32_t qh[Q_WORDS];
-    int n_defer = 0, n_def_l = 0, n_def_w = 0, n_x = 0;
-    int waves_x = 0;
-    XwArgs xa{};
-    // windows wider than 64 (k_lin_xw): one wave per key, up to four per CU
-    // (round 2 capped this at 128 waves); qw: the queue words after k_key_tables
-    auto prep_xw = [&](const int32_t *qw) {
-        if (n_x <= 0) return;
-        uint32_t capx = 1u << 12;
-        while ((int64_t)capx < 2 * budget && capx < (1u << 30)) capx <<= 1;
-        const uint64_t scr_x = (((uint64_t)(uint32_t)qw[26] | ((uint64_t)(uint32_t)qw[27] << 32)) + 255) & ~255ULL;
-        int want_x = std::min(n_x, 4 * ctx->n_cu);
-        if (opts && opts->xw_waves > 0) want_x = std::min(n_x, opts->xw_waves);
-        const uint64_t per_x = (uint64_t)capx * XW_EW * 8 + (uint64_t)stack_cap * XW_FW * 8 + scr_x;
-        waves_x = fit_units(ctx, want_x, per_x, {WS_MEMO_X, WS_STACK_X, WS_SCRATCH_X});
-        const bool freshx = ctx->ws_fresh(WS_MEMO_X) || ctx->bufs[WS_MEMO_X].bytes < (size_t)waves_x * capx * XW_EW * 8;
-        uint64_t *memox = ctx->ws<uint64_t>(WS_MEMO_X, (size_t)waves_x * capx * XW_EW, /*zero=*/true);
-        if (clear_memo && !freshx) HIP_TRY(hipMemsetAsync(memox, 0, ctx->bufs[WS_MEMO_X].bytes, st));
-        xa = XwArgs{};
-        xa.src = KeySrc{rec, pair, off, rB, viol, rank, q + 2};
-        xa.list = list_x; xa.n_list = n_x; xa.queue = q + 21; xa.meta = meta; xa.out = out_dev;
-        xa.scratch = ctx->ws<char>(WS_SCRATCH_X, (size_t)waves_x * scr_x); xa.scratch_bytes = scr_x;
-        xa.memo = memox; xa.memo_cap = capx;
-        xa.stack = ctx->ws<uint64_t>(WS_STACK_X, (size_t)waves_x * stack_cap * XW_FW); xa.stack_cap = stack_cap;
-        xa.budget = budget; xa.init_state = init_state;
-        xa.gen_base = ctx->gen_base + 2 * (uint32_t)K + 1;   // its own table: any gen range works
-        xa.flags = q + 2; xa.probes = (unsigned long long *)(q + 22);
-        xa.cause_or = linear_mode ? CAUSE_BY_WGL : 0;
-        xa.t_span = (unsigned long long *)(q + Q_T_XW);
-    };
+}
 
+// resume (round 5): phase 1's deferred LEAN searches saved for the heavy-key
+// pass (a record is <= 64 B + a frame per stack level + 16 B per insert)
+// (not for the workgroup engine's tuning modes, JH_WG: its
+// searches start at the root, so records would only be written)
+// writes: skip_p1, p1_only, resume; a's rs_*, hlog* and handover_min
+void LinRun::phase1_resume() {
+    skip_p1 = (lflags & JH_LIN_SKIP_PHASE1) != 0 && !linear_mode;
+    p1_only = (lflags & JH_LIN_PHASE1_ONLY) != 0 && !linear_mode && !skip_p1;
+    const bool wg_mode = tune_env("JH_WG") && atoi(tune_env("JH_WG")) != 0;
+    resume = a.defer && !linear_mode && !skip_p1 && !p1_only && !(lflags & JH_LIN_NO_RESUME) &&
+             !(lflags & JH_LIN_STREAM) && !wg_mode &&
+             !tune_env("JH_NO_RESUME");
+    if (!resume) return;
+    if (!ctx->hbm_total) {
+        size_t fr = 0, tot = 0;
+        HIP_TRY(hipMemGetInfo(&fr, &tot));
+        ctx->hbm_total = tot;
+    }
+    // ADVICE r5 / VERDICT r5 item 7: the record arena and the slot log are
+    // bounded by the device's HBM over the contexts sharing it (1/64 each:
+    // 4.5 GB for one context on an MI355X, so the 256 MB cap rules there).
+    // A smaller log only fails saves (those searches restart: same results)
+    const uint64_t rs_lim = (uint64_t)ctx->hbm_total /
+                            (64 * (uint64_t)std::max(ctx->share, device_open_contexts(ctx->device)));
+    const uint64_t per_key = 64 + (uint64_t)stack_cap * sizeof(Frame) + (uint64_t)quick * 16;
+    // (+ 64 MB for the takeovers' records, round 6)
+    const uint64_t cap = std::min<uint64_t>(std::min<uint64_t>((uint64_t)320 << 20, rs_lim),
+                                            (uint64_t)K * per_key + ((uint64_t)64 << 20));
+    a.rs_arena = ctx->ws<uint8_t>(WS_RS_ARENA, cap);
+    a.rs_cap = cap;
+    a.rs_off = ctx->ws<int64_t>(WS_RS_OFF, K);
+    a.rs_used = (unsigned long long *)(q + Q_RS_USED);
+    HIP_TRY(hipMemsetAsync(a.rs_off, 0xFF, (size_t)K * sizeof(int64_t), st));
+    a.rs_mode = 1;
+#ifdef JH_DUP_WRITE
+    {
+        ulonglong2 *mirror = ctx->ws<ulonglong2>(WS_DEFER_INFO + 1, (size_t)1 << 26);
+        HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_dup_base), &mirror, sizeof mirror));
+    }
+#endif
+    if (!tune_env("JH_RS_SCAN")) {
+        a.hlog_cap = (uint32_t)std::min<int64_t>(std::max<int64_t>(quick, 1024), 32768);
+        a.hlog_cap = (uint32_t)std::max<uint64_t>(256, std::min<uint64_t>(a.hlog_cap, rs_lim / (4 * (uint64_t)std::max(1, waves1))));
+        a.hlog = ctx->ws<uint32_t>(WS_RS_LOG, (size_t)waves1 * a.hlog_cap);
+    }
+    // a handed-over search continues where it stopped: the hand-over is free
+    if (!(lflags & JH_LIN_NO_HANDOVER) && !(opts && opts->handover_min) && !tune_env("JH_HANDOVER_MIN"))
+        a.handover_min = HANDOVER_MIN;
+}
+
+// the heavy keys' budgets and table size, phase 3's lists, and which schedule runs
+// writes: p2, cap2, cap2l, defer3, defer3w, use_wg, wg_race, stream_p2
+void LinRun::phase2_budgets() {
     // phase 2 hands a key that reaches P2_BUDGET inserts to phase 3 (when the
     // phase has fewer waves than keys)
-    int64_t p2 = P2_BUDGET;
+    p2 = P2_BUDGET;
     if (opts && opts->phase2_budget > 0) p2 = std::max<int64_t>(quick + 1, opts->phase2_budget);
-    uint32_t cap2 = 1u << 16;
+    cap2 = 1u << 16;
     while ((int64_t)cap2 < 2 * budget && cap2 < (1u << 30)) cap2 <<= 1;
     if (const char *e = tune_env("JH_MEMO_CAP_SHIFT")) cap2 <<= std::max(0, std::min(3, atoi(e)));   // experiments
-    int32_t *defer3 = ctx->ws<int32_t>(WS_DEFER3, 2 * (size_t)(K + 1));
-    int32_t *defer3w = defer3 + (K + 1);
-    int32_t *claim = nullptr;
-    int waves_w = 0, waves2 = 0;
-    int waves3 = 0;                  // phase 3's LEAN waves (full tables; waves2 unless p2_small)
-    uint32_t cap2l = cap2;           // phase 2's LEAN tables (entries per wave)
-    bool p2_small_ok = true;         // (the streaming pass keeps round 4's sizing)
-    bool split3 = false, split3w = false;
-
-    // ---- the deferred WIDE keys (windows of 41-64 members or >= 256 states):
-    // their own pipeline on the fourth stream, beside the LEAN one. As many
-    // waves as keys, up to four per CU and bounded by free HBM (round 2: 32
-    // waves in phase 2 and 128 in phase 3, queued behind the LEAN kernels on
-    // one stream). With a wave per key there is one pass at the full budget;
-    // with fewer, phase 2 stops a key at P2_BUDGET and phase 3 restarts it
-    // (same waves and tables, a fresh generation range), the count of phase
-    // 3's keys read on the device: no host round trip.
-    DfsArgs bw{};
-    auto prep_wide = [&]() {
-        if (n_def_w == 0) return;
-        const uint64_t per_w = (uint64_t)cap2 * 16 + (uint64_t)stack_cap * sizeof(Frame) + SEQW_SCR;
-        int want_w = std::min(n_def_w, 4 * ctx->n_cu);
-        if (opts && opts->wide_waves > 0) want_w = std::min(want_w, opts->wide_waves);
-        waves_w = fit_units(ctx, want_w, per_w, {WS_MEMO_WIDE, WS_STACK_WIDE, WS_SCRATCH_WIDE});
-        const bool freshw = ctx->ws_fresh(WS_MEMO_WIDE) || ctx->bufs[WS_MEMO_WIDE].bytes < (size_t)waves_w * cap2 * 16;
-        uint64_t *memow = ctx->ws<uint64_t>(WS_MEMO_WIDE, (size_t)waves_w * cap2 * 2, /*zero=*/true);
-        if (clear_memo && !freshw) HIP_TRY(hipMemsetAsync(memow, 0, ctx->bufs[WS_MEMO_WIDE].bytes, st));
-        bw = a;
-        bw.handover_min = 0;
-        bw.rs_mode = 0;
-        bw.list = defer_w; bw.n_list = n_def_w; bw.n_list_dev = nullptr; bw.queue = q + 7;
-        bw.defer64 = nullptr; bw.defer_kind = nullptr; bw.defer_kind_count = nullptr;
-        split3w = waves_w < n_def_w && budget > p2;
-        bw.defer = split3w ? 1 : 0; bw.defer_list = defer3w; bw.defer_count = q + Q_DEFER3W;
-        bw.budget = split3w ? p2 : budget; bw.budget_full = split3w ? budget : 0;
-        bw.memo = memow; bw.memo_cap = cap2;
-        bw.stack = ctx->ws<Frame>(WS_STACK_WIDE, (size_t)waves_w * stack_cap);
-        bw.scratch = ctx->ws<char>(WS_SCRATCH_WIDE, (size_t)waves_w * SEQW_SCR);
-        bw.scratch_bytes = SEQW_SCR;
-        bw.gen_base = ctx->gen_base + (uint32_t)K + 1;
-        bw.claim = claim;                    // the BFS may settle a WIDE key with a narrow window
-        bw.probes = (unsigned long long *)(q + Q_PROBES_WIDE);
-        bw.seq_start = nullptr; bw.exit_count = nullptr; bw.dbg = nullptr; bw.defer_time = nullptr;
-        bw.t_span = (unsigned long long *)(q + Q_T_WIDE);
-    };
-    // phase 2 of the WIDE keys alone (paths without the two-role grid), then phase 3
-    auto launch_wide = [&](hipStream_t sw, bool p2) {
-        if (waves_w == 0) return;
-        if (p2) k_lin_seqw<<<waves_w, 64, SEQW_LDS, sw>>>(bw);
-        HIP_TRY(hipGetLastError());
-        if (split3w) {
-            DfsArgs c3 = bw;
-            c3.list = defer3w; c3.n_list = 0; c3.n_list_dev = q + Q_DEFER3W; c3.queue = q + 20; c3.defer = 0;
-            c3.defer_list = nullptr; c3.defer_count = nullptr;
-            c3.budget = budget; c3.budget_full = 0; c3.wave_off = 0;
-            c3.gen_base = ctx->gen_base + 2 * (uint32_t)K + 1;
-            k_lin_seqw<<<waves_w, 64, SEQW_LDS, sw>>>(c3);
-            HIP_TRY(hipGetLastError());
-        }
-    };
-
-    unsigned long long *acc_stats = nullptr;
-    int n_wg = 0;
-    // the workgroup engine (k_lin_wg): exact WGL, dead subtrees enumerated by
-    // the workgroup's helper waves; built for wg_cus CUs, racing the BFS when
-    // wg_claim is set
-    auto build_wg = [&](int wg_cus, int32_t *wg_claim, int32_t *wg_queue, bool all_cus = false) -> WgArgs {
-        acc_stats = ctx->ws<unsigned long long>(WS_ACC_STATS, 8);
-        HIP_TRY(hipMemsetAsync(acc_stats, 0, 8 * sizeof(unsigned long long), st));
-        // + slack: keys claimed in the set after the cap is hit are still recorded
-        const uint64_t work_cap = (uint64_t)std::min<int64_t>(budget, (int64_t)1 << 30) + ACC_MAXROOTS + 16384;
-        uint64_t gcap = 1024;
-        while (gcap < 2 * work_cap) gcap <<= 1;
-        const uint32_t mo = (uint32_t)smax;   // >= n_ok of any key
-        const uint64_t wtab_b = (((uint64_t)(mo + 1) * 4 + 255) & ~255ULL) + (((uint64_t)mo * 40 * 4 + 255) & ~255ULL) +
-                                (((uint64_t)mo + 255) & ~255ULL);
-        const uint64_t per_wg = (uint64_t)cap2 * 16 + gcap * 8 + 3 * work_cap * 8 + (uint64_t)stack_cap * sizeof(Frame) +
-                                MemoW::SLOTS * 8 + wtab_b;
-        uint64_t mem_limit = 48ULL << 30;
-        if (const char *e = tune_env("JH_WG_MEM_GB")) mem_limit = (uint64_t)std::max(1, atoi(e)) << 30;
-        // (with the spec board every helper is useful, a key of its own or not)
-        n_wg = all_cus ? wg_cus : (int)std::min<int64_t>(n_def_l, (int64_t)wg_cus);
-        n_wg = (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)n_wg, mem_limit / per_wg));
-        n_wg = fit_units(ctx, n_wg, per_wg, {WS_WG_MEMO, WS_WG_GSET, WS_WG_WORK, WS_WG_PEND});
-        const bool fresh2 = ctx->ws_fresh(WS_WG_MEMO) || ctx->bufs[WS_WG_MEMO].bytes < (size_t)n_wg * cap2 * 16;
-        uint64_t *memo2 = ctx->ws<uint64_t>(WS_WG_MEMO, (size_t)n_wg * cap2 * 2, /*zero=*/true);
-        if (clear_memo && !fresh2) HIP_TRY(hipMemsetAsync(memo2, 0, ctx->bufs[WS_WG_MEMO].bytes, st));
-        // kept all zero between calls by the enumeration's clean-up
-        uint64_t *gset = ctx->ws<uint64_t>(WS_WG_GSET, (size_t)n_wg * gcap, /*zero=*/true);
-        uint64_t *work = ctx->ws<uint64_t>(WS_WG_WORK, (size_t)n_wg * work_cap, /*zero=*/true);
-        WgArgs wa{};
-        wa.d = a;
-        wa.d.rs_mode = 0;
-        wa.d.handover_min = 0;
-        wa.d.list = defer_l; wa.d.n_list = n_def_l; wa.d.n_list_dev = nullptr; wa.d.queue = wg_queue; wa.d.defer = 0;
-        wa.d.defer_list = nullptr; wa.d.defer_count = nullptr;
-        wa.d.defer64 = nullptr; wa.d.defer_kind = nullptr; wa.d.defer_kind_count = nullptr;
-        wa.d.memo = memo2; wa.d.memo_cap = cap2;
-        wa.d.stack = ctx->ws<Frame>(WS_WG_STACK, (size_t)n_wg * stack_cap);
-        wa.d.scratch = ctx->ws<char>(WS_WG_SCR, (size_t)n_wg * MemoW::SLOTS * 8);
-        wa.d.scratch_bytes = MemoW::SLOTS * 8;
-        wa.d.budget = budget; wa.d.budget_full = 0; wa.d.claim = wg_claim;
-        wa.d.gen_base = ctx->gen_base + (uint32_t)K + 1;
-        wa.d.dbg = nullptr; wa.d.probes = (unsigned long long *)(q + Q_PROBES_HELP);
-        wa.gset = gset; wa.gset_cap = (uint32_t)gcap; wa.work = work; wa.work_cap = (uint32_t)work_cap;
-        wa.wtab = ctx->ws<char>(WS_WG_WTAB, (size_t)n_wg * wtab_b); wa.wtab_bytes = wtab_b;
-        if (dbgenv && atoi(dbgenv) >= 3) {
-            // its own slot: the BFS's JH_DEBUG words live in WS_DEBUG (a shared slot
-            // grown here would leave their pointer dangling)
-            wa.d.dbg = ctx->ws<unsigned long long>(WS_DEBUG_WG, (size_t)n_wg * 256 + 16 * 1024);
-            HIP_TRY(hipMemsetAsync(wa.d.dbg, 0, sizeof(unsigned long long) * n_wg * 256, st));
-        }
-        wa.acc_stats = acc_stats;
-        wa.pend_cap = (uint32_t)work_cap;
-        wa.acc_t = ACC_T;
-        if (const char *e = tune_env("JH_ACC_T")) wa.acc_t = (uint32_t)std::max(0, atoi(e));
-        if (dbgenv && atoi(dbgenv) >= 4) {
-            wa.key_prof = ctx->ws<unsigned long long>(WS_STATS_KEYS, 3 * (size_t)K);
-            HIP_TRY(hipMemsetAsync(wa.key_prof, 0, 3 * sizeof(unsigned long long) * K, st));
-        }
-        wa.pend = ctx->ws<uint64_t>(WS_WG_PEND, (size_t)n_wg * 2 * work_cap);
-        if (!ctx->lds_attr_wg) {
-            HIP_TRY(hipFuncSetAttribute((const void *)k_lin_wg, hipFuncAttributeMaxDynamicSharedMemorySize, WG_LDS));
-            ctx->lds_attr_wg = true;
-        }
-        return wa;
-    };
-    int n_unres = 0;
+    defer3 = ctx->ws<int32_t>(WS_DEFER3, 2 * (size_t)(K + 1));
+    defer3w = defer3 + (K + 1);
+    cap2l = cap2;
     const char *wg_env = tune_env("JH_WG");
     // JH_WG=1 (tuning builds): the workgroup engine (k_lin_wg, exact DFS with
     // accelerated dead subtrees) for deferred LEAN keys; default: the BFS /
     // sequential race
-    const bool use_wg = wg_env && atoi(wg_env) == 1;
+    use_wg = wg_env && atoi(wg_env) == 1;
     // JH_WG=2: the workgroup engine races the BFS in place of the sequential search
-    const bool wg_race = wg_env && atoi(wg_env) == 2;
-    int wg2 = 0, n_help = 0;
-    // the heavy-key race's engines for at most nd_all deferred keys (nd_l of
-    // them LEAN): the BFS (c), the sequential search of the LEAN keys (b),
-    // the late helpers (wh) or the workgroup race (wr); allocations only
-    BfsArgs c{};
-    DfsArgs b{};
-    WgArgs wr{}, wh{};
-    unsigned long long *seq_start = nullptr;
-    uint32_t *seq_stall = nullptr;
-    int p2_per_cu = P2_LEAN_PER_CU;
-    bool p2_m = true, bfs_only = false;
-    auto prep_race = [&](int nd_all, int nd_l) {
-        claim = ctx->ws<int32_t>(WS_CLAIM, K);
-        HIP_TRY(hipMemsetAsync(claim, 0, (size_t)K * sizeof(int32_t), st));
-        // q[0] (phase 1's queue) becomes the BFS's; q[3] its give-up count; q[6] phase 2's queue
-        HIP_TRY(hipMemsetAsync(q, 0, sizeof(int32_t), st));
-        HIP_TRY(hipMemsetAsync(q + 3, 0, sizeof(int32_t), st));
-        HIP_TRY(hipMemsetAsync(q + 6, 0, sizeof(int32_t), st));
-
-        // the BFS enumerates up to reach_cap configurations and keeps up to
-        // ncap of them for WGL's exact count of valid keys (bfs_wgl_count)
-        uint32_t ncap = 1u << 22;
-        if (const char *e = tune_env("JH_BFS_NODES")) ncap = (uint32_t)std::max(1 << 16, std::min(1 << 26, atoi(e)));
-        const int64_t reach_cap = std::max<int64_t>(budget + 1, ncap);
-        uint32_t set_cap = 1u << 12;
-        while ((int64_t)set_cap < 2 * reach_cap && set_cap < (1u << 30)) set_cap <<= 1;
-        const uint32_t q_cap = (uint32_t)std::min<int64_t>(reach_cap + 64, (int64_t)1 << 30);
-        uint32_t hcap = 1u << 16;
-        while (hcap < 2 * (uint64_t)ncap) hcap <<= 1;
-        const uint32_t lcap = (uint32_t)smax + 2;
-        // CU split of the heavy-key pass (one BFS workgroup or one sequential
-        // wave per CU, by LDS): invalid keys are few, the sequential searches
-        // many (every valid deferred key), so most CUs go to the latter
-        // 96 of 256 (round 2, with phase 2 at four waves per CU): C4 shard
-        // 230 -> 223 ms, C3 ranks 0 / 3 / 6 flat (32: C4 +9 %, 128: no better)
-        // Round 6, with 64 helpers: 64 when 2 000-4 000 keys are deferred
-        // (the sequential search keeps 128 CUs for its queue; C3 ranks 0-4,
-        // 3 550-3 750 deferred keys: 39.0 / 36.0 / 35.2 / 39.6 / 45.4 -> 38.1 /
-        // 34.0 / 31.3 / 40.5 / 43.7 ms), 96 for fewer (the strong-scaling
-        // shards' 1 335 / 694 deferred keys: 27.1 / 21.0 -> 24.5 / 19.4 ms) and
-        // for more (C4's shard, 4 258 deferred keys, 812 of them invalid ones
-        // the BFS settles: 209.7 -> 202.0 ms); profiles/r06/ab_bfs_helpers/,
-        // ab_c4_split/. A measured band, not a model of the race.
-        const int bfs_cus = std::max(1, nd_all > 2000 && nd_all <= 4000 ? ctx->n_cu / 4
-                                                                          : std::min(96, ctx->n_cu * 3 / 8));
-        wg2 = std::min(nd_all, tune_env("JH_BFS_CUS") ? std::max(1, atoi(tune_env("JH_BFS_CUS"))) :
-                               opts && opts->bfs_wgs > 0 ? std::min(opts->bfs_wgs, ctx->n_cu - 16) : bfs_cus);
-        const uint64_t per_bfs = (uint64_t)set_cap * 8 + 4ULL * q_cap * 8 + scr_bytes_bfs + (uint64_t)ncap * 8 +
-                                 (uint64_t)lcap * 4 + (uint64_t)hcap * 16 + (uint64_t)ncap * 4 + ((uint64_t)ncap / 32 + 1) * 4 +
-                                 (uint64_t)ncap * 4 + (uint64_t)ncap * 8;
-        wg2 = fit_units(ctx, wg2, per_bfs, {WS_BFS_SET, WS_BFS_Q, WS_BFS_NODES, WS_BFS_HKEY, WS_BFS_TMPK});
-        uint64_t *bset = ctx->ws<uint64_t>(WS_BFS_SET, (size_t)wg2 * set_cap);
-        uint64_t *bq = ctx->ws<uint64_t>(WS_BFS_Q, (size_t)wg2 * 4 * q_cap);
-        char *bscr = ctx->ws<char>(WS_SCRATCH_BFS, (size_t)wg2 * scr_bytes_bfs);
-        int32_t *unres = ctx->ws<int32_t>(WS_BFS_META, nd_all + 1);
-        c = BfsArgs{};
-        c.src = KeySrc{rec, pair, off, rB, viol, rank, q + 2};
-        c.list = defer; c.n_list = nd_all; c.queue = q; c.out = out_dev;
-        c.unres_list = unres; c.unres_count = q + 3;
-        c.gset = bset; c.gset_cap = set_cap; c.pend = bq; c.front = bq + (size_t)wg2 * 2 * q_cap;
-        c.q_cap = q_cap;
-        c.scratch = bscr; c.scratch_bytes = scr_bytes_bfs; c.budget = budget;
-        c.init_state = init_state; c.states_ok = n_states < 4096 ? 1 : 0;
-        c.dbg = dbg; c.claim = claim;
-        // every key the BFS settles carries WGL's exact count (the whole set for
-        // an invalid key; path + dead closure for a valid one, bfs_wgl_count)
-        c.reach_cap = reach_cap;
-        // JH_LIN_BFS_ONLY (tests): no sequential search, the BFS settles every
-        // key it can (the others stay unsettled); JH_BFS_DBGV=1 (tuning builds):
-        // its valid verdicts carry fail_entry = path length, cause = stored
-        // configurations, explored = count
-        bfs_only = (lflags & JH_LIN_BFS_ONLY) != 0;
-        c.dbg_plen = tune_env("JH_BFS_DBGV") && atoi(tune_env("JH_BFS_DBGV")) ? 1 : 0;
-        c.exact_count = (lflags & JH_LIN_EXACT_COUNT) || c.dbg_plen ? 1 : 0;
-        c.ncap = ncap; c.hcap = hcap; c.lcap = lcap;
-        c.nodes = ctx->ws<uint64_t>(WS_BFS_NODES, (size_t)wg2 * ncap);
-        c.lstart = ctx->ws<uint32_t>(WS_BFS_LSTART, (size_t)wg2 * lcap);
-        c.ent = ctx->ws<ulonglong2>(WS_BFS_HKEY, (size_t)wg2 * hcap);
-        c.slot = ctx->ws<uint32_t>(WS_BFS_LIVE, (size_t)wg2 * ncap);
-        c.vis = ctx->ws<uint32_t>(WS_BFS_VIS, (size_t)wg2 * (ncap / 32 + 1));
-        c.tmp = ctx->ws<uint32_t>(WS_BFS_TMP, (size_t)wg2 * ncap);
-        c.tmpk = ctx->ws<uint64_t>(WS_BFS_TMPK, (size_t)wg2 * ncap);
-        // per context (= per device; calls on one context are serialised by its mutex)
-        if (!ctx->lds_attr) {
-            HIP_TRY(hipFuncSetAttribute((const void *)k_lin_bfs, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        BFS_LDS_BYTES));
-            HIP_TRY(hipFuncSetAttribute((const void *)k_lin_seq<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        MemoH::LDS));
-            HIP_TRY(hipFuncSetAttribute((const void *)k_lin_seq<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        MemoH::LDS));
-            ctx->lds_attr = true;
-        }
-
-        // late helpers (k_lin_wg in helper mode, wg_helper_pick): a few CUs
-        // taken from the sequential search of the LEAN keys
-        n_help = bfs_only || wg_race || nd_l == 0 ? 0 : std::min(HELPERS, std::max(0, ctx->n_cu / 4));
-        if (opts && opts->helpers > 0) n_help = std::min(ctx->n_cu / 2, opts->helpers);
-        if (const char *e = tune_env("JH_HELPERS")) n_help = std::max(0, std::min(ctx->n_cu, atoi(e)));
-        if (lflags & JH_LIN_NO_HELPERS) n_help = 0;
-        // JH_HELP_CUS (tuning builds): CUs the sizing of phase 2's sequential
-        // search leaves to the helpers (default: one per helper); helpers
-        // beyond it start when CUs free up
-        int help_cus = n_help;
-        if (const char *e = tune_env("JH_HELP_CUS")) help_cus = std::max(0, std::min(n_help, atoi(e)));
-        if (n_help > 0 && ctx->n_cu - wg2 - help_cus < 16) n_help = help_cus = 0;
-        // phase 2's sequential search with four waves per CU and the 32 KB memo
-        // (k_lin_seq3), p2_waves_per_cu = 1 for one wave per CU and the 128 KB
-        // memo (k_lin_seq): measured C4 shard 268 -> 228 ms, C3 / ranks 3, 6 / C5 flat
-        p2_m = !(opts && opts->p2_waves_per_cu == 1);
-        cap2l = cap2;
-        if (nd_l > 0) {
-            const int cus2 = std::max(1, ctx->n_cu - wg2 - help_cus);
-            // LEAN keys alone in the grid: MemoP2's waves per CU, or the dense
-            // instance's (round 7; p2_waves_per_cu = 3 / 6 selects one)
-            p2_per_cu = P2_LEAN_PER_CU;
-            if (opts && (opts->p2_waves_per_cu == JH_P2_PER_CU || opts->p2_waves_per_cu == P2_DENSE_PER_CU))
-                p2_per_cu = opts->p2_waves_per_cu;
-            const int lean_per_cu = n_def_w > 0 || !p2_small_ok ? 4 : p2_per_cu;
-            int want2 = std::min(nd_l, cus2 * (p2_m ? lean_per_cu : 1));
-            if (opts && opts->lean_waves > 0) want2 = std::min(want2, opts->lean_waves);
-            const uint64_t fixed = (uint64_t)stack_cap * sizeof(Frame) + scr_bytes_h;
-            const uint64_t per2 = (uint64_t)cap2 * 16 + fixed;
-            waves2 = fit_units(ctx, want2, per2, {WS_MEMO_DEEP, WS_STACK_DEEP, WS_SCRATCH_DEEP});
-            waves3 = waves2;
-            // more keys than waves: phase 2 stops at p2 inserts and phase 3
-            // takes the rest on full tables, so phase 2's LEAN role can run
-            // p2_per_cu waves per CU on tables for 2 x p2 entries
-            if (p2_m && p2_small_ok && n_def_w == 0 && !(opts && opts->lean_waves > 0) && budget > p2) {
-                uint32_t cs = 1u << 16;
-                while ((int64_t)cs < 2 * p2 && cs < cap2) cs <<= 1;
-                const int want_s = std::min(nd_l, cus2 * p2_per_cu);
-                const int ws = fit_units(ctx, want_s, (uint64_t)cs * 16 + fixed, {WS_MEMO_DEEP, WS_STACK_DEEP, WS_SCRATCH_DEEP});
-                if (ws < nd_l) {
-                    cap2l = cs;
-                    waves2 = ws;
-                }
-            }
-        }
-        // generation-tagged: zeroed once when allocated (and on wrap), not per
-        // call; phases 2 and 3 share it at their own strides (their generation
-        // ranges differ, so one phase's entries are empty slots to the other's)
-        uint64_t *memo2 = nullptr;
-        const size_t m2 = std::max((size_t)waves2 * cap2l, (size_t)waves3 * cap2);
-        if (waves2 > 0) {
-            const bool fresh2 = ctx->ws_fresh(WS_MEMO_DEEP) || ctx->bufs[WS_MEMO_DEEP].bytes < m2 * 16;
-            memo2 = ctx->ws<uint64_t>(WS_MEMO_DEEP, m2 * 2, /*zero=*/true);
-            if (clear_memo && !fresh2) HIP_TRY(hipMemsetAsync(memo2, 0, ctx->bufs[WS_MEMO_DEEP].bytes, st));
-        }
-        wr = WgArgs{};
-        if (wg_race && nd_l > 0) wr = build_wg(std::max(1, ctx->n_cu - wg2), claim, q + 6);
-        wh = WgArgs{};
-        seq_start = nullptr;
-        seq_stall = nullptr;
-        if (n_help > 0) {
-            const bool spec_on = !(lflags & JH_LIN_NO_SPEC) && !(tune_env("JH_SPEC") && !atoi(tune_env("JH_SPEC")));
-            wh = build_wg(n_help, claim, nullptr, spec_on);
-            seq_start = ctx->ws<unsigned long long>(WS_HELP_START, K);
-            // [0, K): the taken flags; [K, 2K): the sequential searches' stalls (round 7)
-            int32_t *taken = ctx->ws<int32_t>(WS_HELP_TAKEN, 2 * (size_t)K);
-            HIP_TRY(hipMemsetAsync(seq_start, 0, (size_t)K * sizeof(unsigned long long), st));
-            HIP_TRY(hipMemsetAsync(taken, 0, 2 * (size_t)K * sizeof(int32_t), st));
-            seq_stall = (uint32_t *)(taken + K);
-            wh.seq_start = seq_start; wh.seq_exit = q + 28; wh.seq_waves = waves2; wh.taken = taken;
-            wh.mains_live = q + Q_MAINS;
-            uint64_t late_us = HELPER_LATE_US;
-            if (opts && opts->helper_late_us > 0) late_us = (uint64_t)opts->helper_late_us;
-            if (lflags & JH_LIN_HELPERS_NOW) late_us = 0;
-            wh.late_ticks = late_us * 100;     // s_memrealtime: 100 MHz
-            // round 7, the default pick: by the sequential search's published
-            // stall (wg_helper_pick); a caller that sets a delay or one of the
-            // round-6 policies keeps the pick by run time
-            const bool by_time = JH_HELP_BY_ORDER || (opts && opts->helper_late_us > 0) ||
-                                 (lflags & (JH_LIN_HELPERS_NOW | JH_LIN_HELP_STALL));
-            wh.stall = by_time ? nullptr : seq_stall;
-            wh.stall_min = opts && opts->helper_stall_min > 0 ? (uint32_t)opts->helper_stall_min : HELPER_STALL_MIN;
-            // round 6: the spec board (SpecSlot), unless JH_LIN_NO_SPEC
-            if (spec_on) {
-                wh.spec = ctx->ws<SpecSlot>(WS_SPEC, SPEC_SLOTS);
-                HIP_TRY(hipMemsetAsync(wh.spec, 0, sizeof(SpecSlot) * SPEC_SLOTS, st));
-                wh.spec_res_cap = SPEC_RES_CAP;
-                wh.spec_res = ctx->ws<uint64_t>(WS_SPEC_RES, (size_t)n_wg * SPEC_RES_CAP);
-                wh.spec_min = 512; wh.spec_mult = 32; wh.spec_dist = 128;
-                wh.spec_q = q + Q_SPEC;
-                wh.spec_first = (lflags & JH_LIN_SPEC_FIRST) ? 1 : 0;
-                // round 7: at most HELPER_MAINS helpers run keys; the others
-                // serve the board from the start, so a main's first posts find
-                // servers (with every helper a main, the board was served only
-                // by helpers between keys)
-                wh.n_mains = std::min(n_wg, HELPER_MAINS);
-                if (const char *e = tune_env("JH_SPEC_SERVERS")) wh.n_mains = std::max(1, n_wg - std::max(0, atoi(e)));
-                if (const char *e = tune_env("JH_SPEC_MIN")) wh.spec_min = (uint32_t)std::max(1, atoi(e));
-                if (const char *e = tune_env("JH_SPEC_MULT")) wh.spec_mult = (uint32_t)std::max(1, atoi(e));
-                if (const char *e = tune_env("JH_SPEC_DIST")) wh.spec_dist = (uint32_t)std::max(1, atoi(e));
-            }
-        }
-        const int wmax = std::max(waves2, waves3);
-        Frame *stack2 = waves2 > 0 ? ctx->ws<Frame>(WS_STACK_DEEP, (size_t)wmax * stack_cap) : nullptr;
-        char *scr2 = waves2 > 0 ? ctx->ws<char>(WS_SCRATCH_DEEP, (size_t)wmax * scr_bytes_h) : nullptr;
-        // a wave per key: one pass at the full budget; fewer waves than keys:
-        // phase 2 stops at p2 inserts and phase 3 restarts those keys
-        split3 = waves2 < nd_l && budget > p2;
-        b = a;
-        b.rs_mode = 0;                  // the default race below continues phase 1's records
-        b.handover_min = 0;
-        b.list = defer_l; b.n_list = nd_l; b.n_list_dev = nullptr; b.queue = q + 6; b.defer = split3 ? 1 : 0;
-        b.defer_list = defer3; b.defer_count = q + 16;
-        b.defer64 = nullptr; b.defer_kind = nullptr; b.defer_kind_count = nullptr;
-        b.memo = memo2; b.memo_cap = cap2l; b.stack = stack2; b.scratch = scr2; b.scratch_bytes = scr_bytes_h;
-        b.budget = split3 ? p2 : budget;
-        // (past p2 a search goes on while the queue is empty, on full tables only)
-        b.budget_full = split3 && cap2l == cap2 ? budget : 0;
-        b.gen_base = ctx->gen_base + (uint32_t)K + 1;
-        b.dbg = dbg ? dbg + 16 * 256 : nullptr; b.claim = claim;
-        b.probes = (unsigned long long *)(q + 8);
-        b.seq_start = seq_start; b.exit_count = seq_start ? q + 28 : nullptr;
-        b.stamp_progress = seq_start && (lflags & JH_LIN_HELP_STALL) ? 1 : 0;
-        b.stall = seq_stall;
-        b.defer_time = nullptr;
-        // round 6, the takeover: a late helper continues the sequential
-        // search's record (phase 2's own slot log, 32 K entries per wave)
-        // instead of restarting the key
-        b.handoff = nullptr;
-        // (opt-in, JH_LIN_TAKEOVER: one exact-count call of sixteen final
-        // lines disagreed with the oracle with it on, unexplained)
-        if (n_help > 0 && a.rs_off && waves2 > 0 && (lflags & JH_LIN_TAKEOVER) && !(lflags & JH_LIN_NO_TAKEOVER)) {
-            int32_t *ho = ctx->ws<int32_t>(WS_HANDOFF, K);
-            HIP_TRY(hipMemsetAsync(ho, 0, (size_t)K * sizeof(int32_t), st));
-            b.handoff = ho;
-            b.hlog_cap = 32768;
-            b.hlog = ctx->ws<uint32_t>(WS_RS_LOG2, (size_t)wmax * b.hlog_cap);
-            wh.d.handoff = ho;
-        }
-    };
+    wg_race = wg_env && atoi(wg_env) == 2;
     // the streaming heavy-key pass (round 4) whenever the default race runs
-    const bool stream_p2 = !linear_mode && !skip_p1 && !p1_only && !use_wg && !wg_race && !dbg2 &&
-                           (lflags & JH_LIN_STREAM) && !(lflags & JH_LIN_BFS_ONLY);
-    if (stream_p2) {
-        // ---- the streaming heavy-key pass (round 4) --------------------------
-        // Round 3 started the heavy keys when phase 1 ended (~17 ms into C3),
-        // though most were deferred at 9-13 ms. Here phase 1 appends every key
-        // it defers to live lists; once its last kernel's queue is drained (each
-        // of its waves then finishes the key it holds and leaves) the host
-        // launches the consumers -- the BFS (aux2), the late helpers (aux3) and
-        // an early grid of LEAN sequential waves (aux) -- which take CUs as
-        // phase 1 frees them and take keys as they are deferred. A grid behind
-        // phase 1 on st runs the 65-256-member keys, the WIDE keys and more LEAN
-        // waves; phase 3 follows on st. Four streams: the hardware's queues.
-        // Every search is the one the round-3 schedule runs (same verdicts and
-        // counts); only when each starts changes.
-        // (round 4's CU-masked variant, JH_CU_SPLIT, is gone: slower at every
-        // split, and at R = 48 the late helpers -- which spin until the
-        // sequential grid has left its queue -- held the 48 consumer CUs the
-        // sequential waves needed to become resident, so each step waited out
-        // HELPER_MAX_TICKS, 5 s: DESIGN.md section 5)
-        hipStream_t p1s = st, cs1 = ctx->aux, cs2 = ctx->aux2, cs3 = ctx->aux3;
-        int32_t qt[Q_WORDS];
-        HIP_TRY(hipMemcpyAsync(qt, q, sizeof qt, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        const int n_l1 = qt[12], n_w1 = qt[13];
-        n_x = qt[19];
-        prep_xw(qt);
-        // bounds: phase 1 defers at most the keys it searches
-        n_def_l = n_l1; n_def_w = n_w1; n_defer = n_l1 + n_w1;
-        int w_early = 0;
-        const bool any = n_defer > 0;
-        if (any) {
-            HIP_TRY(hipMemsetAsync(defer, 0xFF, 3 * sizeof(int32_t) * (size_t)(K + 1), st));   // live lists: -1 = not yet
-            p2_small_ok = false;
-            prep_race(n_defer, n_def_l);
-            prep_wide();
-            c.list = defer; c.n_list = 0; c.queue = q + Q_BFS_QUEUE;
-            c.live_n = q + 1; c.p1_done = q + Q_P1_DONE; c.p1_tot = q + 12;
-            c.t_span = (unsigned long long *)(q + Q_T_BFS);
-            b.list = defer_l; b.n_list = 0; b.live_n = q + Q_DEFER_L; b.p1_done = q + Q_P1_DONE; b.p1_tot = q + 12;
-            b.s_all = nullptr; b.s_kind = nullptr; b.drained = nullptr; b.wave_off = 0;
-            b.t_span = (unsigned long long *)(q + Q_T_LEAN);
-            if (waves_w > 0) {
-                bw.list = defer_w; bw.n_list = 0; bw.live_n = q + Q_DEFER_W; bw.p1_done = q + Q_P1_DONE; bw.p1_tot = q + 12;
-                bw.s_all = nullptr; bw.s_kind = nullptr; bw.drained = nullptr;
-            }
-            if (n_help > 0) {
-                wh.d.list = defer_l; wh.d.n_list = 0; wh.d.live_n = q + Q_DEFER_L;
-                wh.d.p1_done = q + Q_P1_DONE; wh.d.p1_tot = q + 12;
-                wh.d.s_all = nullptr; wh.d.s_kind = nullptr; wh.d.drained = nullptr;
-                wh.seq_waves_dev = q + Q_SEQ_WAVES;
-            }
-            // the early LEAN grid: enough waves for the keys deferred while
-            // phase 1 runs (C3: ~120), few enough to leave the BFS whole CUs
-            w_early = std::min(waves2, EARLY_LEAN_WAVES);
-            if (const char *e = tune_env("JH_EARLY_LEAN")) w_early = std::min(waves2, std::max(0, atoi(e)));
-            const int32_t sw = waves2;
-            HIP_TRY(hipMemcpyAsync(q + Q_SEQ_WAVES, &sw, sizeof sw, hipMemcpyHostToDevice, st));
-            if (defer_times) {
-                // tuning builds: per key [BFS start, BFS end, sequential start, end]
-                unsigned long long *tl = ctx->ws<unsigned long long>(WS_TL, TL_W * (size_t)K);
-                HIP_TRY(hipMemsetAsync(tl, 0, TL_W * sizeof(unsigned long long) * K, st));
-                c.tl = tl; b.tl = tl;
-                if (n_help > 0) wh.d.tl = tl;
-            }
-        }
-        // phase-1 producer side: live lists, finished-key count, drain flag
-        if (!ctx->hflag) {
-            HIP_TRY(hipHostMalloc((void **)&ctx->hflag, 64, hipHostMallocMapped | hipHostMallocCoherent));
-            HIP_TRY(hipHostGetDevicePointer((void **)&ctx->hflag_dev, ctx->hflag, 0));
-        }
-        *(volatile int32_t *)ctx->hflag = 0;
-        a.p1_count = q + Q_P1_DONE;
-        if (any) { a.s_all = defer; a.s_kind = defer_l; }
-        DfsArgs aw = a;
-        aw.list = list_w; aw.n_list_dev = q + 13; aw.queue = q + 14;
-        aw.defer_kind = d64 + 2 * (K + 1); aw.defer_kind_count = q + Q_DEFER_W;
-        if (any) aw.s_kind = defer_w;
-        // the last phase-1 kernel with keys raises the flag (WIDE keys run
-        // after the LEAN kernel: then consumers start at the WIDE drain)
-        a.drained = n_w1 == 0 ? ctx->hflag_dev : nullptr;
-        aw.drained = n_w1 > 0 ? ctx->hflag_dev : nullptr;
-        a.t_span = (unsigned long long *)(q + Q_T_P1);
-        HIP_TRY(hipEventRecord(ctx->ev[6], st));     // fork: tables, lists and counters are ready
-        HIP_TRY(hipEventRecord(ctx->ev[1], st));
-        if (p1s != st) HIP_TRY(hipStreamWaitEvent(p1s, ctx->ev[6], 0));
-        k_lin_dfs<true, true><<<waves1, 64, MemoQ::LDS, p1s>>>(a);
+    stream_p2 = !linear_mode && !skip_p1 && !p1_only && !use_wg && !wg_race && !dbg2 &&
+                (lflags & JH_LIN_STREAM) && !(lflags & JH_LIN_BFS_ONLY);
+}
+
+// ---------------------------------------------------------------------------
+// The heavy-key engines' arguments and tables (allocations only, no launch).
+
+// >64 KB dynamic LDS for the BFS and the lone-wave sequential search
+// per context (= per device; calls on one context are serialised by its mutex)
+void LinRun::ensure_lds_attrs() {
+    if (ctx->lds_attr) return;
+    HIP_TRY(hipFuncSetAttribute((const void *)k_lin_bfs, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                BFS_LDS_BYTES));
+    HIP_TRY(hipFuncSetAttribute((const void *)k_lin_seq<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                MemoH::LDS));
+    HIP_TRY(hipFuncSetAttribute((const void *)k_lin_seq<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                MemoH::LDS));
+    ctx->lds_attr = true;
+}
+
+// windows wider than 64 (k_lin_xw): one wave per key, up to four per CU
+// (round 2 capped this at 128 waves); qw: the queue words after k_key_tables
+// writes: waves_x, xa
+void LinRun::prep_xw(const int32_t *qw) {
+    if (n_x <= 0) return;
+    uint32_t capx = 1u << 12;
+    while ((int64_t)capx < 2 * budget && capx < (1u << 30)) capx <<= 1;
+    const uint64_t scr_x = ((uint64_t)q64(qw, Q_XW_MAX) + 255) & ~255ULL;
+    int want_x = std::min(n_x, 4 * ctx->n_cu);
+    if (opts && opts->xw_waves > 0) want_x = std::min(n_x, opts->xw_waves);
+    const uint64_t per_x = (uint64_t)capx * XW_EW * 8 + (uint64_t)stack_cap * XW_FW * 8 + scr_x;
+    waves_x = fit_units(ctx, want_x, per_x, {WS_MEMO_X, WS_STACK_X, WS_SCRATCH_X});
+    const bool freshx = ctx->ws_fresh(WS_MEMO_X) || ctx->bufs[WS_MEMO_X].bytes < (size_t)waves_x * capx * XW_EW * 8;
+    uint64_t *memox = ctx->ws<uint64_t>(WS_MEMO_X, (size_t)waves_x * capx * XW_EW, /*zero=*/true);
+    if (clear_memo && !freshx) HIP_TRY(hipMemsetAsync(memox, 0, ctx->bufs[WS_MEMO_X].bytes, st));
+    xa = XwArgs{};
+    xa.src = key_src();
+    xa.list = list_x; xa.n_list = n_x; xa.queue = q + Q_XW_QUEUE; xa.meta = meta; xa.out = out_dev;
+    xa.scratch = ctx->ws<char>(WS_SCRATCH_X, (size_t)waves_x * scr_x); xa.scratch_bytes = scr_x;
+    xa.memo = memox; xa.memo_cap = capx;
+    xa.stack = ctx->ws<uint64_t>(WS_STACK_X, (size_t)waves_x * stack_cap * XW_FW); xa.stack_cap = stack_cap;
+    xa.budget = budget; xa.init_state = init_state;
+    xa.gen_base = ctx->gen_base + 2 * (uint32_t)K + 1;   // its own table: any gen range works
+    xa.flags = q + Q_FLAGS; xa.probes = (unsigned long long *)(q + Q_PROBES_XW);
+    xa.cause_or = linear_mode ? CAUSE_BY_WGL : 0;
+    xa.t_span = (unsigned long long *)(q + Q_T_XW);
+}
+
+// ---- the deferred WIDE keys (windows of 41-64 members or >= 256 states):
+// their own pipeline on the fourth stream, beside the LEAN one. As many
+// waves as keys, up to four per CU and bounded by free HBM (round 2: 32
+// waves in phase 2 and 128 in phase 3, queued behind the LEAN kernels on
+// one stream). With a wave per key there is one pass at the full budget;
+// with fewer, phase 2 stops a key at P2_BUDGET and phase 3 restarts it
+// (same waves and tables, a fresh generation range), the count of phase
+// 3's keys read on the device: no host round trip.
+// writes: waves_w, split3w, bw
+void LinRun::prep_wide() {
+    if (n_def_w == 0) return;
+    const uint64_t per_w = (uint64_t)cap2 * 16 + (uint64_t)stack_cap * sizeof(Frame) + SEQW_SCR;
+    int want_w = std::min(n_def_w, 4 * ctx->n_cu);
+    if (opts && opts->wide_waves > 0) want_w = std::min(want_w, opts->wide_waves);
+    waves_w = fit_units(ctx, want_w, per_w, {WS_MEMO_WIDE, WS_STACK_WIDE, WS_SCRATCH_WIDE});
+    const bool freshw = ctx->ws_fresh(WS_MEMO_WIDE) || ctx->bufs[WS_MEMO_WIDE].bytes < (size_t)waves_w * cap2 * 16;
+    uint64_t *memow = ctx->ws<uint64_t>(WS_MEMO_WIDE, (size_t)waves_w * cap2 * 2, /*zero=*/true);
+    if (clear_memo && !freshw) HIP_TRY(hipMemsetAsync(memow, 0, ctx->bufs[WS_MEMO_WIDE].bytes, st));
+    bw = a;
+    bw.handover_min = 0;
+    bw.rs_mode = 0;
+    bw.list = defer_w; bw.n_list = n_def_w; bw.n_list_dev = nullptr; bw.queue = q + Q_WIDE_QUEUE;
+    bw.defer64 = nullptr; bw.defer_kind = nullptr; bw.defer_kind_count = nullptr;
+    split3w = waves_w < n_def_w && budget > p2;
+    bw.defer = split3w ? 1 : 0; bw.defer_list = defer3w; bw.defer_count = q + Q_DEFER3W;
+    bw.budget = split3w ? p2 : budget; bw.budget_full = split3w ? budget : 0;
+    bw.memo = memow; bw.memo_cap = cap2;
+    bw.stack = ctx->ws<Frame>(WS_STACK_WIDE, (size_t)waves_w * stack_cap);
+    bw.scratch = ctx->ws<char>(WS_SCRATCH_WIDE, (size_t)waves_w * SEQW_SCR);
+    bw.scratch_bytes = SEQW_SCR;
+    bw.gen_base = ctx->gen_base + (uint32_t)K + 1;
+    bw.claim = claim;                    // the BFS may settle a WIDE key with a narrow window
+    bw.probes = (unsigned long long *)(q + Q_PROBES_WIDE);
+    bw.seq_start = nullptr; bw.exit_count = nullptr; bw.dbg = nullptr; bw.defer_time = nullptr;
+    bw.t_span = (unsigned long long *)(q + Q_T_WIDE);
+}
+
+// phase 3 of the WIDE keys: the ones phase 2 handed over, full budget, on
+// phase 2's waves and tables. (The span words stay: outside the streaming
+// pass the WIDE span covers both phases.)
+DfsArgs LinRun::phase3_wide_args() const {
+    DfsArgs c3 = bw;
+    c3.list = defer3w; c3.n_list = 0; c3.n_list_dev = q + Q_DEFER3W; c3.queue = q + Q_P3W_QUEUE; c3.defer = 0;
+    c3.defer_list = nullptr; c3.defer_count = nullptr;
+    c3.budget = budget; c3.budget_full = 0; c3.wave_off = 0;
+    c3.gen_base = ctx->gen_base + 2 * (uint32_t)K + 1;
+    return c3;
+}
+
+// phase 2 of the WIDE keys alone (paths without the two-role grid), then phase 3
+void LinRun::launch_wide(hipStream_t sw, bool p2) {
+    if (waves_w == 0) return;
+    if (p2) k_lin_seqw<<<waves_w, 64, SEQW_LDS, sw>>>(bw);
+    HIP_TRY(hipGetLastError());
+    if (split3w) {
+        k_lin_seqw<<<waves_w, 64, SEQW_LDS, sw>>>(phase3_wide_args());
         HIP_TRY(hipGetLastError());
-        k_lin_dfs<false, true><<<std::min(waves1, 1024), 64, MemoQ::LDS, p1s>>>(aw);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(ctx->ev[4], p1s));
-        if (p1s != st) HIP_TRY(hipStreamWaitEvent(st, ctx->ev[4], 0));
-        a.prio_ins = 0;
-        // behind phase 1 on st: xw keys, WIDE keys, LEAN waves past the early grid's
-        const int late_l = any ? waves2 - w_early : 0;
-        const int n_late = waves_x + waves_w + late_l;
-        if (n_late > 0) {
-            DfsTriple tr{};
-            tr.x = xa; tr.n_x = waves_x;
-            tr.w = bw; tr.w.wave_off = waves_x; tr.n_w = waves_w;
-            tr.l = b; tr.l.wave_off = waves_x + waves_w - w_early;   // its waves use tables w_early..waves2-1
-            const int lds = std::max(SEQLW_LDS, XW_LDS);
-            k_lin_seq_lwx<<<n_late, 64, lds, st>>>(tr);
-            HIP_TRY(hipGetLastError());
+    }
+}
+
+// the workgroup engine (k_lin_wg): exact WGL, dead subtrees enumerated by
+// the workgroup's helper waves; built for wg_cus CUs, racing the BFS when
+// wg_claim is set
+// writes: acc_stats, n_wg, ctx->lds_attr_wg
+WgArgs LinRun::build_wg(int wg_cus, int32_t *wg_claim, int32_t *wg_queue, bool all_cus) {
+    acc_stats = ctx->ws<unsigned long long>(WS_ACC_STATS, 8);
+    HIP_TRY(hipMemsetAsync(acc_stats, 0, 8 * sizeof(unsigned long long), st));
+    // + slack: keys claimed in the set after the cap is hit are still recorded
+    const uint64_t work_cap = (uint64_t)std::min<int64_t>(budget, (int64_t)1 << 30) + ACC_MAXROOTS + 16384;
+    uint64_t gcap = 1024;
+    while (gcap < 2 * work_cap) gcap <<= 1;
+    const uint32_t mo = (uint32_t)smax;   // >= n_ok of any key
+    const uint64_t wtab_b = (((uint64_t)(mo + 1) * 4 + 255) & ~255ULL) + (((uint64_t)mo * 40 * 4 + 255) & ~255ULL) +
+                            (((uint64_t)mo + 255) & ~255ULL);
+    const uint64_t per_wg = (uint64_t)cap2 * 16 + gcap * 8 + 3 * work_cap * 8 + (uint64_t)stack_cap * sizeof(Frame) +
+                            MemoW::SLOTS * 8 + wtab_b;
+    uint64_t mem_limit = 48ULL << 30;
+    if (const char *e = tune_env("JH_WG_MEM_GB")) mem_limit = (uint64_t)std::max(1, atoi(e)) << 30;
+    // (with the spec board every helper is useful, a key of its own or not)
+    n_wg = all_cus ? wg_cus : (int)std::min<int64_t>(n_def_l, (int64_t)wg_cus);
+    n_wg = (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)n_wg, mem_limit / per_wg));
+    n_wg = fit_units(ctx, n_wg, per_wg, {WS_WG_MEMO, WS_WG_GSET, WS_WG_WORK, WS_WG_PEND});
+    const bool fresh2 = ctx->ws_fresh(WS_WG_MEMO) || ctx->bufs[WS_WG_MEMO].bytes < (size_t)n_wg * cap2 * 16;
+    uint64_t *memo2 = ctx->ws<uint64_t>(WS_WG_MEMO, (size_t)n_wg * cap2 * 2, /*zero=*/true);
+    if (clear_memo && !fresh2) HIP_TRY(hipMemsetAsync(memo2, 0, ctx->bufs[WS_WG_MEMO].bytes, st));
+    // kept all zero between calls by the enumeration's clean-up
+    uint64_t *gset = ctx->ws<uint64_t>(WS_WG_GSET, (size_t)n_wg * gcap, /*zero=*/true);
+    uint64_t *work = ctx->ws<uint64_t>(WS_WG_WORK, (size_t)n_wg * work_cap, /*zero=*/true);
+    WgArgs wa{};
+    wa.d = a;
+    wa.d.rs_mode = 0;
+    wa.d.handover_min = 0;
+    wa.d.list = defer_l; wa.d.n_list = n_def_l; wa.d.n_list_dev = nullptr; wa.d.queue = wg_queue; wa.d.defer = 0;
+    wa.d.defer_list = nullptr; wa.d.defer_count = nullptr;
+    wa.d.defer64 = nullptr; wa.d.defer_kind = nullptr; wa.d.defer_kind_count = nullptr;
+    wa.d.memo = memo2; wa.d.memo_cap = cap2;
+    wa.d.stack = ctx->ws<Frame>(WS_WG_STACK, (size_t)n_wg * stack_cap);
+    wa.d.scratch = ctx->ws<char>(WS_WG_SCR, (size_t)n_wg * MemoW::SLOTS * 8);
+    wa.d.scratch_bytes = MemoW::SLOTS * 8;
+    wa.d.budget = budget; wa.d.budget_full = 0; wa.d.claim = wg_claim;
+    wa.d.gen_base = ctx->gen_base + (uint32_t)K + 1;
+    wa.d.dbg = nullptr; wa.d.probes = (unsigned long long *)(q + Q_PROBES_HELP);
+    wa.gset = gset; wa.gset_cap = (uint32_t)gcap; wa.work = work; wa.work_cap = (uint32_t)work_cap;
+    wa.wtab = ctx->ws<char>(WS_WG_WTAB, (size_t)n_wg * wtab_b); wa.wtab_bytes = wtab_b;
+    if (dbgenv && atoi(dbgenv) >= 3) {
+        // its own slot: the BFS's JH_DEBUG words live in WS_DEBUG (a shared slot
+        // grown here would leave their pointer dangling)
+        wa.d.dbg = ctx->ws<unsigned long long>(WS_DEBUG_WG, (size_t)n_wg * 256 + 16 * 1024);
+        HIP_TRY(hipMemsetAsync(wa.d.dbg, 0, sizeof(unsigned long long) * n_wg * 256, st));
+    }
+    wa.acc_stats = acc_stats;
+    wa.pend_cap = (uint32_t)work_cap;
+    wa.acc_t = ACC_T;
+    if (const char *e = tune_env("JH_ACC_T")) wa.acc_t = (uint32_t)std::max(0, atoi(e));
+    if (dbgenv && atoi(dbgenv) >= 4) {
+        wa.key_prof = ctx->ws<unsigned long long>(WS_STATS_KEYS, 3 * (size_t)K);
+        HIP_TRY(hipMemsetAsync(wa.key_prof, 0, 3 * sizeof(unsigned long long) * K, st));
+    }
+    wa.pend = ctx->ws<uint64_t>(WS_WG_PEND, (size_t)n_wg * 2 * work_cap);
+    if (!ctx->lds_attr_wg) {
+        HIP_TRY(hipFuncSetAttribute((const void *)k_lin_wg, hipFuncAttributeMaxDynamicSharedMemorySize, WG_LDS));
+        ctx->lds_attr_wg = true;
+    }
+    return wa;
+}
+
+// The heavy-key race's engines for at most nd_all deferred keys (nd_l of
+// them LEAN): the BFS (c), the sequential search of the LEAN keys (b),
+// the late helpers (wh) or the workgroup race (wr); allocations only.
+// The order is the order of the allocations and fit_units queries.
+void LinRun::prep_race(int nd_all, int nd_l) {
+    race_bfs(nd_all);
+    const int help_cus = race_helper_count(nd_l);
+    uint64_t *memo2 = race_lean_sizing(nd_l, help_cus);
+    race_helpers(nd_l);
+    race_lean_args(nd_l, memo2);
+}
+
+// the claims, the race's queues, and the BFS: its CUs (wg2) and tables
+// writes: claim, wg2, c, bfs_only
+void LinRun::race_bfs(int nd_all) {
+    claim = ctx->ws<int32_t>(WS_CLAIM, K);
+    HIP_TRY(hipMemsetAsync(claim, 0, (size_t)K * sizeof(int32_t), st));
+    // phase 1's queue becomes the BFS's; its give-up count; phase 2's queue
+    HIP_TRY(hipMemsetAsync(q + Q_QUEUE, 0, sizeof(int32_t), st));
+    HIP_TRY(hipMemsetAsync(q + Q_UNRES, 0, sizeof(int32_t), st));
+    HIP_TRY(hipMemsetAsync(q + Q_P2_QUEUE, 0, sizeof(int32_t), st));
+
+    // the BFS enumerates up to reach_cap configurations and keeps up to
+    // ncap of them for WGL's exact count of valid keys (bfs_wgl_count)
+    uint32_t ncap = 1u << 22;
+    if (const char *e = tune_env("JH_BFS_NODES")) ncap = (uint32_t)std::max(1 << 16, std::min(1 << 26, atoi(e)));
+    const int64_t reach_cap = std::max<int64_t>(budget + 1, ncap);
+    const BfsSizes sz = bfs_table_sizes(reach_cap);
+    const uint32_t set_cap = sz.set_cap, q_cap = sz.q_cap;
+    uint32_t hcap = 1u << 16;
+    while (hcap < 2 * (uint64_t)ncap) hcap <<= 1;
+    const uint32_t lcap = (uint32_t)smax + 2;
+    // CU split of the heavy-key pass (one BFS workgroup or one sequential
+    // wave per CU, by LDS): invalid keys are few, the sequential searches
+    // many (every valid deferred key), so most CUs go to the latter
+    // 96 of 256 (round 2, with phase 2 at four waves per CU): C4 shard
+    // 230 -> 223 ms, C3 ranks 0 / 3 / 6 flat (32: C4 +9 %, 128: no better)
+    // Round 6, with 64 helpers: 64 when 2 000-4 000 keys are deferred
+    // (the sequential search keeps 128 CUs for its queue; C3 ranks 0-4,
+    // 3 550-3 750 deferred keys: 39.0 / 36.0 / 35.2 / 39.6 / 45.4 -> 38.1 /
+    // 34.0 / 31.3 / 40.5 / 43.7 ms), 96 for fewer (the strong-scaling
+    // shards' 1 335 / 694 deferred keys: 27.1 / 21.0 -> 24.5 / 19.4 ms) and
+    // for more (C4's shard, 4 258 deferred keys, 812 of them invalid ones
+    // the BFS settles: 209.7 -> 202.0 ms); profiles/r06/ab_bfs_helpers/,
+    // ab_c4_split/. A measured band, not a model of the race.
+    const int bfs_cus = std::max(1, nd_all > 2000 && nd_all <= 4000 ? ctx->n_cu / 4
+                                                                      : std::min(96, ctx->n_cu * 3 / 8));
+    wg2 = std::min(nd_all, tune_env("JH_BFS_CUS") ? std::max(1, atoi(tune_env("JH_BFS_CUS"))) :
+                           opts && opts->bfs_wgs > 0 ? std::min(opts->bfs_wgs, ctx->n_cu - 16) : bfs_cus);
+    const uint64_t per_bfs = (uint64_t)set_cap * 8 + 4ULL * q_cap * 8 + scr_bytes_bfs + (uint64_t)ncap * 8 +
+                             (uint64_t)lcap * 4 + (uint64_t)hcap * 16 + (uint64_t)ncap * 4 + ((uint64_t)ncap / 32 + 1) * 4 +
+                             (uint64_t)ncap * 4 + (uint64_t)ncap * 8;
+    wg2 = fit_units(ctx, wg2, per_bfs, {WS_BFS_SET, WS_BFS_Q, WS_BFS_NODES, WS_BFS_HKEY, WS_BFS_TMPK});
+    uint64_t *bset = ctx->ws<uint64_t>(WS_BFS_SET, (size_t)wg2 * set_cap);
+    uint64_t *bq = ctx->ws<uint64_t>(WS_BFS_Q, (size_t)wg2 * 4 * q_cap);
+    char *bscr = ctx->ws<char>(WS_SCRATCH_BFS, (size_t)wg2 * scr_bytes_bfs);
+    int32_t *unres = ctx->ws<int32_t>(WS_BFS_META, nd_all + 1);
+    c = BfsArgs{};
+    c.src = key_src();
+    c.list = defer; c.n_list = nd_all; c.queue = q + Q_QUEUE; c.out = out_dev;
+    c.unres_list = unres; c.unres_count = q + Q_UNRES;
+    c.gset = bset; c.gset_cap = set_cap; c.pend = bq; c.front = bq + (size_t)wg2 * 2 * q_cap;
+    c.q_cap = q_cap;
+    c.scratch = bscr; c.scratch_bytes = scr_bytes_bfs; c.budget = budget;
+    c.init_state = init_state; c.states_ok = n_states < 4096 ? 1 : 0;
+    c.dbg = dbg; c.claim = claim;
+    // every key the BFS settles carries WGL's exact count (the whole set for
+    // an invalid key; path + dead closure for a valid one, bfs_wgl_count)
+    c.reach_cap = reach_cap;
+    // JH_LIN_BFS_ONLY (tests): no sequential search, the BFS settles every
+    // key it can (the others stay unsettled); JH_BFS_DBGV=1 (tuning builds):
+    // its valid verdicts carry fail_entry = path length, cause = stored
+    // configurations, explored = count
+    bfs_only = (lflags & JH_LIN_BFS_ONLY) != 0;
+    c.dbg_plen = tune_env("JH_BFS_DBGV") && atoi(tune_env("JH_BFS_DBGV")) ? 1 : 0;
+    c.exact_count = (lflags & JH_LIN_EXACT_COUNT) || c.dbg_plen ? 1 : 0;
+    c.ncap = ncap; c.hcap = hcap; c.lcap = lcap;
+    c.nodes = ctx->ws<uint64_t>(WS_BFS_NODES, (size_t)wg2 * ncap);
+    c.lstart = ctx->ws<uint32_t>(WS_BFS_LSTART, (size_t)wg2 * lcap);
+    c.ent = ctx->ws<ulonglong2>(WS_BFS_HKEY, (size_t)wg2 * hcap);
+    c.slot = ctx->ws<uint32_t>(WS_BFS_LIVE, (size_t)wg2 * ncap);
+    c.vis = ctx->ws<uint32_t>(WS_BFS_VIS, (size_t)wg2 * (ncap / 32 + 1));
+    c.tmp = ctx->ws<uint32_t>(WS_BFS_TMP, (size_t)wg2 * ncap);
+    c.tmpk = ctx->ws<uint64_t>(WS_BFS_TMPK, (size_t)wg2 * ncap);
+    ensure_lds_attrs();
+}
+
+// late helpers (k_lin_wg in helper mode, wg_helper_pick): a few CUs taken
+// from the sequential search of the LEAN keys. Sets n_help; returns the CUs
+// the sizing of phase 2's sequential search leaves to them.
+// writes: n_help (reads wg2: after race_bfs)
+int LinRun::race_helper_count(int nd_l) {
+    n_help = bfs_only || wg_race || nd_l == 0 ? 0 : std::min(HELPERS, std::max(0, ctx->n_cu / 4));
+    if (opts && opts->helpers > 0) n_help = std::min(ctx->n_cu / 2, opts->helpers);
+    if (const char *e = tune_env("JH_HELPERS")) n_help = std::max(0, std::min(ctx->n_cu, atoi(e)));
+    if (lflags & JH_LIN_NO_HELPERS) n_help = 0;
+    // JH_HELP_CUS (tuning builds): CUs the sizing of phase 2's sequential
+    // search leaves to the helpers (default: one per helper); helpers
+    // beyond it start when CUs free up
+    int help_cus = n_help;
+    if (const char *e = tune_env("JH_HELP_CUS")) help_cus = std::max(0, std::min(n_help, atoi(e)));
+    if (n_help > 0 && ctx->n_cu - wg2 - help_cus < 16) n_help = help_cus = 0;
+    return help_cus;
+}
+
+// phase 2's (and 3's) LEAN waves and table size, and their memo (returned;
+// null without LEAN waves)
+// writes: p2_m, p2_per_cu, cap2l, waves2, waves3 (reads wg2)
+uint64_t *LinRun::race_lean_sizing(int nd_l, int help_cus) {
+    // phase 2's sequential search with four waves per CU and the 32 KB memo
+    // (k_lin_seq3), p2_waves_per_cu = 1 for one wave per CU and the 128 KB
+    // memo (k_lin_seq): measured C4 shard 268 -> 228 ms, C3 / ranks 3, 6 / C5 flat
+    p2_m = !(opts && opts->p2_waves_per_cu == 1);
+    cap2l = cap2;
+    if (nd_l > 0) {
+        const int cus2 = std::max(1, ctx->n_cu - wg2 - help_cus);
+        // LEAN keys alone in the grid: MemoP2's waves per CU, or the dense
+        // instance's (round 7; p2_waves_per_cu = 3 / 6 selects one)
+        p2_per_cu = P2_LEAN_PER_CU;
+        if (opts && (opts->p2_waves_per_cu == JH_P2_PER_CU || opts->p2_waves_per_cu == P2_DENSE_PER_CU))
+            p2_per_cu = opts->p2_waves_per_cu;
+        const int lean_per_cu = n_def_w > 0 || !p2_small_ok ? 4 : p2_per_cu;
+        int want2 = std::min(nd_l, cus2 * (p2_m ? lean_per_cu : 1));
+        if (opts && opts->lean_waves > 0) want2 = std::min(want2, opts->lean_waves);
+        const uint64_t fixed = (uint64_t)stack_cap * sizeof(Frame) + scr_bytes_h;
+        const uint64_t per2 = (uint64_t)cap2 * 16 + fixed;
+        waves2 = fit_units(ctx, want2, per2, {WS_MEMO_DEEP, WS_STACK_DEEP, WS_SCRATCH_DEEP});
+        waves3 = waves2;
+        // more keys than waves: phase 2 stops at p2 inserts and phase 3
+        // takes the rest on full tables, so phase 2's LEAN role can run
+        // p2_per_cu waves per CU on tables for 2 x p2 entries
+        if (p2_m && p2_small_ok && n_def_w == 0 && !(opts && opts->lean_waves > 0) && budget > p2) {
+            uint32_t cs = 1u << 16;
+            while ((int64_t)cs < 2 * p2 && cs < cap2) cs <<= 1;
+            const int want_s = std::min(nd_l, cus2 * p2_per_cu);
+            const int ws = fit_units(ctx, want_s, (uint64_t)cs * 16 + fixed, {WS_MEMO_DEEP, WS_STACK_DEEP, WS_SCRATCH_DEEP});
+            if (ws < nd_l) {
+                cap2l = cs;
+                waves2 = ws;
+            }
         }
-        HIP_TRY(hipEventRecord(ctx->ev[10], st));
-        if (any) {
-            // the consumers, once phase 1's queue is drained: until then phase
-            // 1 holds every CU, and a consumer launched earlier could take CUs
-            // from it while it still has keys to hand out
-            volatile int32_t *hf = (volatile int32_t *)ctx->hflag;
-            while (!*hf) {
-                const hipError_t e = hipEventQuery(ctx->ev[4]);
-                if (e == hipSuccess) break;
-                if (e != hipErrorNotReady) HIP_TRY(e);
-                std::this_thread::yield();
-            }
-            HIP_TRY(hipStreamWaitEvent(cs2, ctx->ev[6], 0));
-            k_lin_bfs<<<wg2, BFS_THREADS, BFS_LDS_BYTES, cs2>>>(c);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipEventRecord(ctx->ev[5], cs2));
-            if (n_help > 0) {
-                HIP_TRY(hipStreamWaitEvent(cs3, ctx->ev[6], 0));
-                k_lin_wg<<<n_wg, WG_THREADS, WG_LDS, cs3>>>(wh);
-                HIP_TRY(hipGetLastError());
-                HIP_TRY(hipEventRecord(ctx->ev[12], cs3));
-            }
-            HIP_TRY(hipStreamWaitEvent(cs1, ctx->ev[6], 0));
-            if (w_early > 0) {
-                DfsPair pr{};
-                pr.l = b; pr.n_l = w_early;
-                k_lin_seq_lw<true><<<w_early, 64, SEQLW_LDS, cs1>>>(pr);
-                HIP_TRY(hipGetLastError());
-            }
-            HIP_TRY(hipEventRecord(ctx->ev[11], cs1));
-            // phase 3 after every phase-2 wave (both grids hand keys to it)
-            HIP_TRY(hipStreamWaitEvent(st, ctx->ev[11], 0));
-            HIP_TRY(hipEventRecord(ctx->ev[13], st));
-            if (split3) {
-                DfsArgs c3 = b;
-                c3.list = defer3; c3.n_list = 0; c3.n_list_dev = q + 16; c3.defer = 0; c3.live_n = nullptr;
-                c3.defer_list = nullptr; c3.defer_count = nullptr;
-                c3.seq_start = nullptr; c3.exit_count = nullptr; c3.stall = nullptr; c3.t_span = nullptr; c3.wave_off = 0;
-                c3.budget = budget; c3.budget_full = 0; c3.handoff = nullptr;
-                c3.gen_base = ctx->gen_base + 2 * (uint32_t)K + 1;
-                c3.dbg = nullptr;
-                c3.probes = (unsigned long long *)(q + Q_PROBES_P3);
-                const int few = std::max(1, ctx->n_cu - wg2);
-                DfsArgs c3a = c3;
-                c3a.queue = q + 17; c3a.n_max = few;
-                k_lin_seq<true><<<std::min(waves2, few), 64, MemoH::LDS, st>>>(c3a);
-                HIP_TRY(hipGetLastError());
-                DfsArgs c3b = c3;
-                c3b.queue = q + 18; c3b.n_min = few + 1;
-                k_lin_seq3<true><<<waves2, 64, MemoM::LDS, st>>>(c3b);
-                HIP_TRY(hipGetLastError());
-            }
-            if (split3w) {
-                DfsArgs c3 = bw;
-                c3.list = defer3w; c3.n_list = 0; c3.n_list_dev = q + Q_DEFER3W; c3.queue = q + 20; c3.defer = 0;
-                c3.live_n = nullptr; c3.t_span = nullptr;
-                c3.defer_list = nullptr; c3.defer_count = nullptr;
-                c3.budget = budget; c3.budget_full = 0; c3.wave_off = 0;
-                c3.gen_base = ctx->gen_base + 2 * (uint32_t)K + 1;
-                k_lin_seqw<<<waves_w, 64, SEQW_LDS, st>>>(c3);
-                HIP_TRY(hipGetLastError());
-            }
-            HIP_TRY(hipEventRecord(ctx->ev[7], st));
-            HIP_TRY(hipStreamWaitEvent(st, ctx->ev[5], 0));
-            if (n_help > 0) HIP_TRY(hipStreamWaitEvent(st, ctx->ev[12], 0));
-        } else {
-            HIP_TRY(hipEventRecord(ctx->ev[13], st));
-            HIP_TRY(hipEventRecord(ctx->ev[7], st));
-        }
-        // entries per list (the phases' rooflines), the lists' lengths on the device
-        EntryLists el{};
-        el.list[0] = defer; el.n_dev[0] = q + 1; el.sum[0] = (unsigned long long *)(q + Q_ENT_ALL);
-        el.list[1] = defer_l; el.n_dev[1] = q + Q_DEFER_L; el.sum[1] = (unsigned long long *)(q + Q_ENT_LEAN);
-        el.list[2] = defer_w; el.n_dev[2] = q + Q_DEFER_W; el.sum[2] = (unsigned long long *)(q + Q_ENT_WIDE);
-        el.list[3] = list_x; el.n[3] = n_x; el.sum[3] = (unsigned long long *)(q + Q_ENT_XW);
-        el.list[4] = defer3; el.n_dev[4] = q + 16; el.sum[4] = (unsigned long long *)(q + Q_ENT_P3);
-        el.off = off;
-        k_list_entries<<<dim3(16, 5), 256, 0, st>>>(el);
+    }
+    // generation-tagged: zeroed once when allocated (and on wrap), not per
+    // call; phases 2 and 3 share it at their own strides (their generation
+    // ranges differ, so one phase's entries are empty slots to the other's)
+    uint64_t *memo2 = nullptr;
+    const size_t m2 = std::max((size_t)waves2 * cap2l, (size_t)waves3 * cap2);
+    if (waves2 > 0) {
+        const bool fresh2 = ctx->ws_fresh(WS_MEMO_DEEP) || ctx->bufs[WS_MEMO_DEEP].bytes < m2 * 16;
+        memo2 = ctx->ws<uint64_t>(WS_MEMO_DEEP, m2 * 2, /*zero=*/true);
+        if (clear_memo && !fresh2) HIP_TRY(hipMemsetAsync(memo2, 0, ctx->bufs[WS_MEMO_DEEP].bytes, st));
+    }
+    return memo2;
+}
+
+// the workgroup race (JH_WG=2) or the late helpers: their engine, the
+// sequential searches' start times and stalls, the spec board
+// writes: wr, wh, seq_start, seq_stall, and build_wg's (reads n_help, waves2: after the sizing)
+void LinRun::race_helpers(int nd_l) {
+    wr = WgArgs{};
+    if (wg_race && nd_l > 0) wr = build_wg(std::max(1, ctx->n_cu - wg2), claim, q + Q_P2_QUEUE);
+    wh = WgArgs{};
+    seq_start = nullptr;
+    seq_stall = nullptr;
+    if (n_help <= 0) return;
+    const bool spec_on = !(lflags & JH_LIN_NO_SPEC) && !(tune_env("JH_SPEC") && !atoi(tune_env("JH_SPEC")));
+    wh = build_wg(n_help, claim, nullptr, spec_on);
+    seq_start = ctx->ws<unsigned long long>(WS_HELP_START, K);
+    // [0, K): the taken flags; [K, 2K): the sequential searches' stalls (round 7)
+    int32_t *taken = ctx->ws<int32_t>(WS_HELP_TAKEN, 2 * (size_t)K);
+    HIP_TRY(hipMemsetAsync(seq_start, 0, (size_t)K * sizeof(unsigned long long), st));
+    HIP_TRY(hipMemsetAsync(taken, 0, 2 * (size_t)K * sizeof(int32_t), st));
+    seq_stall = (uint32_t *)(taken + K);
+    wh.seq_start = seq_start; wh.seq_exit = q + Q_SEQ_EXIT; wh.seq_waves = waves2; wh.taken = taken;
+    wh.mains_live = q + Q_MAINS;
+    uint64_t late_us = HELPER_LATE_US;
+    if (opts && opts->helper_late_us > 0) late_us = (uint64_t)opts->helper_late_us;
+    if (lflags & JH_LIN_HELPERS_NOW) late_us = 0;
+    wh.late_ticks = late_us * 100;     // s_memrealtime: 100 MHz
+    // round 7, the default pick: by the sequential search's published
+    // stall (wg_helper_pick); a caller that sets a delay or one of the
+    // round-6 policies keeps the pick by run time
+    const bool by_time = JH_HELP_BY_ORDER || (opts && opts->helper_late_us > 0) ||
+                         (lflags & (JH_LIN_HELPERS_NOW | JH_LIN_HELP_STALL));
+    wh.stall = by_time ? nullptr : seq_stall;
+    wh.stall_min = opts && opts->helper_stall_min > 0 ? (uint32_t)opts->helper_stall_min : HELPER_STALL_MIN;
+    // round 6: the spec board (SpecSlot), unless JH_LIN_NO_SPEC
+    if (spec_on) {
+        wh.spec = ctx->ws<SpecSlot>(WS_SPEC, SPEC_SLOTS);
+        HIP_TRY(hipMemsetAsync(wh.spec, 0, sizeof(SpecSlot) * SPEC_SLOTS, st));
+        wh.spec_res_cap = SPEC_RES_CAP;
+        wh.spec_res = ctx->ws<uint64_t>(WS_SPEC_RES, (size_t)n_wg * SPEC_RES_CAP);
+        wh.spec_min = 512; wh.spec_mult = 32; wh.spec_dist = 128;
+        wh.spec_q = q + Q_SPEC;
+        wh.spec_first = (lflags & JH_LIN_SPEC_FIRST) ? 1 : 0;
+        // round 7: at most HELPER_MAINS helpers run keys; the others
+        // serve the board from the start, so a main's first posts find
+        // servers (with every helper a main, the board was served only
+        // by helpers between keys)
+        wh.n_mains = std::min(n_wg, HELPER_MAINS);
+        if (const char *e = tune_env("JH_SPEC_SERVERS")) wh.n_mains = std::max(1, n_wg - std::max(0, atoi(e)));
+        if (const char *e = tune_env("JH_SPEC_MIN")) wh.spec_min = (uint32_t)std::max(1, atoi(e));
+        if (const char *e = tune_env("JH_SPEC_MULT")) wh.spec_mult = (uint32_t)std::max(1, atoi(e));
+        if (const char *e = tune_env("JH_SPEC_DIST")) wh.spec_dist = (uint32_t)std::max(1, atoi(e));
+    }
+}
+
+// the LEAN sequential search's stacks and arguments (b), the split into
+// phases 2 and 3, the takeover's buffers
+// writes: split3, b, wh.d.handoff (reads seq_start, seq_stall: after race_helpers)
+void LinRun::race_lean_args(int nd_l, uint64_t *memo2) {
+    const int wmax = std::max(waves2, waves3);
+    Frame *stack2 = waves2 > 0 ? ctx->ws<Frame>(WS_STACK_DEEP, (size_t)wmax * stack_cap) : nullptr;
+    char *scr2 = waves2 > 0 ? ctx->ws<char>(WS_SCRATCH_DEEP, (size_t)wmax * scr_bytes_h) : nullptr;
+    // a wave per key: one pass at the full budget; fewer waves than keys:
+    // phase 2 stops at p2 inserts and phase 3 restarts those keys
+    split3 = waves2 < nd_l && budget > p2;
+    b = a;
+    b.rs_mode = 0;                  // the default race continues phase 1's records (run_race)
+    b.handover_min = 0;
+    b.list = defer_l; b.n_list = nd_l; b.n_list_dev = nullptr; b.queue = q + Q_P2_QUEUE; b.defer = split3 ? 1 : 0;
+    b.defer_list = defer3; b.defer_count = q + Q_DEFER3;
+    b.defer64 = nullptr; b.defer_kind = nullptr; b.defer_kind_count = nullptr;
+    b.memo = memo2; b.memo_cap = cap2l; b.stack = stack2; b.scratch = scr2; b.scratch_bytes = scr_bytes_h;
+    b.budget = split3 ? p2 : budget;
+    // (past p2 a search goes on while the queue is empty, on full tables only)
+    b.budget_full = split3 && cap2l == cap2 ? budget : 0;
+    b.gen_base = ctx->gen_base + (uint32_t)K + 1;
+    b.dbg = dbg ? dbg + 16 * 256 : nullptr; b.claim = claim;
+    b.probes = (unsigned long long *)(q + Q_PROBES_SEQ);
+    b.seq_start = seq_start; b.exit_count = seq_start ? q + Q_SEQ_EXIT : nullptr;
+    b.stamp_progress = seq_start && (lflags & JH_LIN_HELP_STALL) ? 1 : 0;
+    b.stall = seq_stall;
+    b.defer_time = nullptr;
+    // round 6, the takeover: a late helper continues the sequential
+    // search's record (phase 2's own slot log, 32 K entries per wave)
+    // instead of restarting the key
+    b.handoff = nullptr;
+    // (opt-in, JH_LIN_TAKEOVER: one exact-count call of sixteen final
+    // lines disagreed with the oracle with it on, unexplained)
+    if (n_help > 0 && a.rs_off && waves2 > 0 && (lflags & JH_LIN_TAKEOVER) && !(lflags & JH_LIN_NO_TAKEOVER)) {
+        int32_t *ho = ctx->ws<int32_t>(WS_HANDOFF, K);
+        HIP_TRY(hipMemsetAsync(ho, 0, (size_t)K * sizeof(int32_t), st));
+        b.handoff = ho;
+        b.hlog_cap = 32768;
+        b.hlog = ctx->ws<uint32_t>(WS_RS_LOG2, (size_t)wmax * b.hlog_cap);
+        wh.d.handoff = ho;
+    }
+}
+
+// tuning builds (JH_DEFER_TIMES): per key [BFS start, end, sequential start,
+// end, helper start, end]
+// writes: the tl fields of c, b, wh.d and (wide) bw
+void LinRun::timeline_tables(bool wide) {
+    if (!defer_times) return;
+    unsigned long long *tl = ctx->ws<unsigned long long>(WS_TL, TL_W * (size_t)K);
+    HIP_TRY(hipMemsetAsync(tl, 0, TL_W * sizeof(unsigned long long) * K, st));
+    c.tl = tl; b.tl = tl;
+    if (wide) bw.tl = tl;
+    if (n_help > 0) wh.d.tl = tl;
+}
+
+// phase 1's second kernel: the WIDE keys, after the LEAN ones, on the same waves
+DfsArgs LinRun::phase1_wide_args() const {
+    DfsArgs aw = a;
+    aw.list = list_w; aw.n_list_dev = q + Q_N_LIST_W; aw.queue = q + Q_P1W_QUEUE;
+    aw.defer_kind = d64 + 2 * (K + 1); aw.defer_kind_count = q + Q_DEFER_W;
+    return aw;
+}
+
+// Phase 3: the LEAN keys phase 2 handed over, full budget, on phase 2's
+// tables at their full size (same stream, phase 2 has ended; a fresh
+// generation range). One copy for the race and the streaming pass: the
+// race's b never has live_n, t_span or wave_off set, and the streaming pass
+// sizes phase 2 with full tables (p2_small_ok is off: cap2l == cap2), so
+// each assignment below is what that schedule assigned or leaves its value.
+DfsArgs LinRun::phase3_lean_args() const {
+    DfsArgs c3 = b;
+    c3.list = defer3; c3.n_list = 0; c3.n_list_dev = q + Q_DEFER3; c3.defer = 0; c3.live_n = nullptr;
+    c3.defer_list = nullptr; c3.defer_count = nullptr;
+    c3.seq_start = nullptr; c3.exit_count = nullptr; c3.stall = nullptr; c3.t_span = nullptr; c3.wave_off = 0;
+    c3.budget = budget; c3.budget_full = 0; c3.handoff = nullptr;
+    c3.memo_cap = cap2;
+    c3.gen_base = ctx->gen_base + 2 * (uint32_t)K + 1;
+    c3.dbg = nullptr;
+    c3.probes = (unsigned long long *)(q + Q_PROBES_P3);
+    return c3;
+}
+
+// entries per list: the phases' rooflines (56 B per entry of the keys they
+// search). live: the streaming pass, the lists' lengths read on the device
+void LinRun::entry_lists(bool live) {
+    EntryLists el{};
+    el.list[0] = defer; el.sum[0] = (unsigned long long *)(q + Q_ENT_ALL);
+    el.list[1] = defer_l; el.sum[1] = (unsigned long long *)(q + Q_ENT_LEAN);
+    el.list[2] = defer_w; el.sum[2] = (unsigned long long *)(q + Q_ENT_WIDE);
+    el.list[3] = list_x; el.n[3] = n_x; el.sum[3] = (unsigned long long *)(q + Q_ENT_XW);
+    if (live) {
+        el.n_dev[0] = q + Q_DEFER; el.n_dev[1] = q + Q_DEFER_L; el.n_dev[2] = q + Q_DEFER_W;
+        el.list[4] = defer3; el.n_dev[4] = q + Q_DEFER3; el.sum[4] = (unsigned long long *)(q + Q_ENT_P3);
     } else {
-        HIP_TRY(hipEventRecord(ctx->ev[1], st));
-        if (!linear_mode && !skip_p1) {
-            k_lin_dfs<true, false><<<waves1, 64, MemoQ::LDS, st>>>(a);
-            HIP_TRY(hipGetLastError());
-            DfsArgs aw = a;
-            aw.list = list_w; aw.n_list_dev = q + 13; aw.queue = q + 14;
-            aw.defer_kind = d64 + 2 * (K + 1); aw.defer_kind_count = q + Q_DEFER_W;
-            k_lin_dfs<false, false><<<std::min(waves1, 1024), 64, MemoQ::LDS, st>>>(aw);
-            a.prio_ins = 0;                       // the heavy-key passes inherit a: no priorities there
-        } else if (cfgreq) {
-            k_req_lists<<<1, 1, 0, st>>>(cfgreq->keys_dev, cfgreq->n_q, K, defer, defer_l, q);
-        } else {
-            // :linear, or stage 2 of a two-stage check: every key that needs a
-            // search is a heavy key
-            k_linear_lists<<<1, 1024, 0, st>>>(list, q + 12, list_w, q + 13, defer, defer_l, defer_w, q);
+        el.n[0] = n_defer; el.n[1] = n_def_l; el.n[2] = n_def_w;
+    }
+    el.off = off;
+    k_list_entries<<<dim3(16, live ? 5 : 4), 256, 0, st>>>(el);
+}
+
+// no heavy keys: the events the summary reads, all at once
+void LinRun::record_no_heavy_keys() {
+    HIP_TRY(hipEventRecord(ctx->ev[EV_FORK], st));
+    HIP_TRY(hipEventRecord(ctx->ev[EV_BFS_END], st));
+    HIP_TRY(hipEventRecord(ctx->ev[EV_P2_END], st));
+    HIP_TRY(hipEventRecord(ctx->ev[EV_SEQ_END], st));
+}
+
+// ---------------------------------------------------------------------------
+// The schedules.
+
+// ---- the streaming heavy-key pass (round 4) --------------------------
+// Round 3 started the heavy keys when phase 1 ended (~17 ms into C3),
+// though most were deferred at 9-13 ms. Here phase 1 appends every key
+// it defers to live lists; once its last kernel's queue is drained (each
+// of its waves then finishes the key it holds and leaves) the host
+// launches the consumers -- the BFS (aux2), the late helpers (aux3) and
+// an early grid of LEAN sequential waves (aux) -- which take CUs as
+// phase 1 frees them and take keys as they are deferred. A grid behind
+// phase 1 on st runs the 65-256-member keys, the WIDE keys and more LEAN
+// waves; phase 3 follows on st. Four streams: the hardware's queues.
+// Every search is the one the round-3 schedule runs (same verdicts and
+// counts); only when each starts changes.
+// (round 4's CU-masked variant, JH_CU_SPLIT, is gone: slower at every
+// split, and at R = 48 the late helpers -- which spin until the
+// sequential grid has left its queue -- held the 48 consumer CUs the
+// sequential waves needed to become resident, so each step waited out
+// HELPER_MAX_TICKS, 5 s: DESIGN.md section 5)
+// writes: n_x, n_defer, n_def_l, n_def_w (bounds until finish), p2_small_ok, the live-list fields of a, c, b, bw, wh; and prep_xw's, prep_race's, prep_wide's
+void LinRun::run_streaming() {
+    hipStream_t p1s = st, cs1 = ctx->aux, cs2 = ctx->aux2, cs3 = ctx->aux3;
+    int32_t qt[Q_WORDS];
+    HIP_TRY(hipMemcpyAsync(qt, q, sizeof qt, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const int n_l1 = qt[Q_N_LIST], n_w1 = qt[Q_N_LIST_W];
+    n_x = qt[Q_N_LIST_X];
+    prep_xw(qt);
+    // bounds: phase 1 defers at most the keys it searches
+    n_def_l = n_l1; n_def_w = n_w1; n_defer = n_l1 + n_w1;
+    int w_early = 0;
+    const bool any = n_defer > 0;
+    if (any) {
+        HIP_TRY(hipMemsetAsync(defer, 0xFF, 3 * sizeof(int32_t) * (size_t)(K + 1), st));   // live lists: -1 = not yet
+        p2_small_ok = false;
+        prep_race(n_defer, n_def_l);
+        prep_wide();
+        c.list = defer; c.n_list = 0; c.queue = q + Q_BFS_QUEUE;
+        c.live_n = q + Q_DEFER; c.p1_done = q + Q_P1_DONE; c.p1_tot = q + Q_N_LIST;
+        c.t_span = (unsigned long long *)(q + Q_T_BFS);
+        b.list = defer_l; b.n_list = 0; b.live_n = q + Q_DEFER_L; b.p1_done = q + Q_P1_DONE; b.p1_tot = q + Q_N_LIST;
+        b.s_all = nullptr; b.s_kind = nullptr; b.drained = nullptr; b.wave_off = 0;
+        b.t_span = (unsigned long long *)(q + Q_T_LEAN);
+        if (waves_w > 0) {
+            bw.list = defer_w; bw.n_list = 0; bw.live_n = q + Q_DEFER_W; bw.p1_done = q + Q_P1_DONE; bw.p1_tot = q + Q_N_LIST;
+            bw.s_all = nullptr; bw.s_kind = nullptr; bw.drained = nullptr;
         }
-        a.prio_ins = 0;
+        if (n_help > 0) {
+            wh.d.list = defer_l; wh.d.n_list = 0; wh.d.live_n = q + Q_DEFER_L;
+            wh.d.p1_done = q + Q_P1_DONE; wh.d.p1_tot = q + Q_N_LIST;
+            wh.d.s_all = nullptr; wh.d.s_kind = nullptr; wh.d.drained = nullptr;
+            wh.seq_waves_dev = q + Q_SEQ_WAVES;
+        }
+        // the early LEAN grid: enough waves for the keys deferred while
+        // phase 1 runs (C3: ~120), few enough to leave the BFS whole CUs
+        w_early = std::min(waves2, EARLY_LEAN_WAVES);
+        if (const char *e = tune_env("JH_EARLY_LEAN")) w_early = std::min(waves2, std::max(0, atoi(e)));
+        const int32_t sw = waves2;
+        HIP_TRY(hipMemcpyAsync(q + Q_SEQ_WAVES, &sw, sizeof sw, hipMemcpyHostToDevice, st));
+        timeline_tables(/*wide=*/false);
+    }
+    // phase-1 producer side: live lists, finished-key count, drain flag
+    if (!ctx->hflag) {
+        HIP_TRY(hipHostMalloc((void **)&ctx->hflag, 64, hipHostMallocMapped | hipHostMallocCoherent));
+        HIP_TRY(hipHostGetDevicePointer((void **)&ctx->hflag_dev, ctx->hflag, 0));
+    }
+    *(volatile int32_t *)ctx->hflag = 0;
+    a.p1_count = q + Q_P1_DONE;
+    if (any) { a.s_all = defer; a.s_kind = defer_l; }
+    DfsArgs aw = phase1_wide_args();
+    if (any) aw.s_kind = defer_w;
+    // the last phase-1 kernel with keys raises the flag (WIDE keys run
+    // after the LEAN kernel: then consumers start at the WIDE drain)
+    a.drained = n_w1 == 0 ? ctx->hflag_dev : nullptr;
+    aw.drained = n_w1 > 0 ? ctx->hflag_dev : nullptr;
+    a.t_span = (unsigned long long *)(q + Q_T_P1);
+    HIP_TRY(hipEventRecord(ctx->ev[EV_FORK], st));     // fork: tables, lists and counters are ready
+    HIP_TRY(hipEventRecord(ctx->ev[EV_P1_START], st));
+    if (p1s != st) HIP_TRY(hipStreamWaitEvent(p1s, ctx->ev[EV_FORK], 0));
+    k_lin_dfs<true, true><<<waves1, 64, MemoQ::LDS, p1s>>>(a);
+    HIP_TRY(hipGetLastError());
+    k_lin_dfs<false, true><<<std::min(waves1, 1024), 64, MemoQ::LDS, p1s>>>(aw);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ctx->ev[EV_P1_END], p1s));
+    if (p1s != st) HIP_TRY(hipStreamWaitEvent(st, ctx->ev[EV_P1_END], 0));
+    a.prio_ins = 0;
+    // behind phase 1 on st: xw keys, WIDE keys, LEAN waves past the early grid's
+    const int late_l = any ? waves2 - w_early : 0;
+    const int n_late = waves_x + waves_w + late_l;
+    if (n_late > 0) {
+        DfsTriple tr{};
+        tr.x = xa; tr.n_x = waves_x;
+        tr.w = bw; tr.w.wave_off = waves_x; tr.n_w = waves_w;
+        tr.l = b; tr.l.wave_off = waves_x + waves_w - w_early;   // its waves use tables w_early..waves2-1
+        const int lds = std::max(SEQLW_LDS, XW_LDS);
+        k_lin_seq_lwx<<<n_late, 64, lds, st>>>(tr);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(ctx->ev[4], st));
-        HIP_TRY(hipMemcpyAsync(qh, q, sizeof qh, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        n_defer = qh[1]; n_def_l = qh[Q_DEFER_L]; n_def_w = qh[Q_DEFER_W];
-        n_x = cfgreq ? 0 : qh[19];
-        if (n_def_l + n_def_w != n_defer) throw_jh(JH_EDEVICE, "deferred-key lists disagree");
-        if (n_defer > 0 && !linear_mode && !skip_p1) {
-            // heavy keys, heaviest estimate first (the likely longest searches start
-            // first), sorted on the device: no host round trip between the phases
-            // (stage 1 of a two-stage check reads the list too: k_mark_deferred)
-            SortLists sl{};
-            const int nn[3] = {n_defer, n_def_l, n_def_w};
-            int32_t *outs[3] = {defer, defer_l, defer_w};
-            for (int i = 0; i < 3; i++) { sl.in[i] = d64 + (size_t)i * (K + 1); sl.out[i] = outs[i]; sl.n[i] = nn[i]; }
-            k_sort_defer<<<3, 1024, 0, st>>>(sl);
-            for (int i = 0; i < 3; i++) {
-                if (nn[i] <= SORT_SMALL) continue;
-                uint64_t *tk = ctx->ws<uint64_t>(WS_DEFER64_T, (size_t)K + 1);
-                size_t tbs = 0;
-                HIP_TRY(hipcub::DeviceRadixSort::SortKeys(nullptr, tbs, sl.in[i], tk, nn[i], 0, 64, st));
-                HIP_TRY(hipcub::DeviceRadixSort::SortKeys(ctx->ws<char>(WS_LTMP, tbs), tbs, sl.in[i], tk, nn[i], 0, 64, st));
-                k_unpack_keys<<<grid_for(nn[i], 256), 256, 0, st>>>(tk, nn[i], outs[i]);
-            }
+    }
+    HIP_TRY(hipEventRecord(ctx->ev[EV_P2_END], st));
+    if (any) {
+        // the consumers, once phase 1's queue is drained: until then phase
+        // 1 holds every CU, and a consumer launched earlier could take CUs
+        // from it while it still has keys to hand out
+        volatile int32_t *hf = (volatile int32_t *)ctx->hflag;
+        while (!*hf) {
+            const hipError_t e = hipEventQuery(ctx->ev[EV_P1_END]);
+            if (e == hipSuccess) break;
+            if (e != hipErrorNotReady) HIP_TRY(e);
+            std::this_thread::yield();
         }
-        if (n_defer > 0 || n_x > 0) {
-            // entries per list: the phases' rooflines (56 B per entry of the keys they search)
-            EntryLists el{};
-            el.list[0] = defer; el.n[0] = n_defer; el.sum[0] = (unsigned long long *)(q + Q_ENT_ALL);
-            el.list[1] = defer_l; el.n[1] = n_def_l; el.sum[1] = (unsigned long long *)(q + Q_ENT_LEAN);
-            el.list[2] = defer_w; el.n[2] = n_def_w; el.sum[2] = (unsigned long long *)(q + Q_ENT_WIDE);
-            el.list[3] = list_x; el.n[3] = n_x; el.sum[3] = (unsigned long long *)(q + Q_ENT_XW);
-        el.list[4] = nullptr; el.n[4] = 0;
-            el.off = off;
-            k_list_entries<<<dim3(16, 4), 256, 0, st>>>(el);
-        }
-        if (dbg2) {
-            std::vector<unsigned long long> h((size_t)waves1 * 16);
-            HIP_TRY(hipMemcpy(h.data(), dbg, h.size() * 8, hipMemcpyDeviceToHost));
-            unsigned long long tot[16] = {0}, mx9 = 0;
-            for (int w = 0; w < waves1; w++) { for (int k = 0; k < 16; k++) tot[k] += h[16 * w + k]; mx9 = std::max(mx9, h[16 * w + 9]); }
-            fprintf(stderr, "[jh-dfs] waves=%d keys=%llu search=%.0f cyc/key | steps=%llu inserts=%llu evict=%llu lay-loads=%llu op-loads=%llu spills=%llu refills=%llu slow=%llu hbm-probes=%llu hbm-inserts=%llu | cyc/step=%.0f | wave-busy avg=%.0f max=%llu cyc\n",
-                    waves1, tot[3], (double)tot[2] / std::max(1ULL, tot[3]), tot[4], tot[5], tot[6], tot[7], tot[10],
-                    tot[11], tot[12], tot[13], tot[14], tot[8], (double)tot[2] / std::max(1ULL, tot[4]), (double)tot[9] / waves1, mx9);
-            HIP_TRY(hipMemsetAsync(dbg, 0, sizeof(unsigned long long) * (waves1 + 512) * 16, st));
-        }
-        // stage 1 of a two-stage check: the 65-256-member keys are heavy keys
-        // too -- they come back deferred (progress 0) for the pool, unsearched
-        if (n_x > 0 && p1_only) {
-            k_mark_list_deferred<<<grid_for(n_x, 256), 256, 0, st>>>(list_x, n_x, out_dev);
+        HIP_TRY(hipStreamWaitEvent(cs2, ctx->ev[EV_FORK], 0));
+        k_lin_bfs<<<wg2, BFS_THREADS, BFS_LDS_BYTES, cs2>>>(c);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(ctx->ev[EV_BFS_END], cs2));
+        if (n_help > 0) {
+            HIP_TRY(hipStreamWaitEvent(cs3, ctx->ev[EV_FORK], 0));
+            k_lin_wg<<<n_wg, WG_THREADS, WG_LDS, cs3>>>(wh);
             HIP_TRY(hipGetLastError());
-            n_x = 0;
+            HIP_TRY(hipEventRecord(ctx->ev[EV_HELP_END], cs3));
         }
-        // windows wider than 64: k_lin_xw on the third stream, alongside phases 2 and 3
+        HIP_TRY(hipStreamWaitEvent(cs1, ctx->ev[EV_FORK], 0));
+        if (w_early > 0) {
+            DfsPair pr{};
+            pr.l = b; pr.n_l = w_early;
+            k_lin_seq_lw<true><<<w_early, 64, SEQLW_LDS, cs1>>>(pr);
+            HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(hipEventRecord(ctx->ev[EV_EARLY_END], cs1));
+        // phase 3 after every phase-2 wave (both grids hand keys to it)
+        HIP_TRY(hipStreamWaitEvent(st, ctx->ev[EV_EARLY_END], 0));
+        HIP_TRY(hipEventRecord(ctx->ev[EV_P3_START], st));
+        if (split3) launch_phase3_lean(waves2, st);
+        if (split3w) {
+            DfsArgs c3 = phase3_wide_args();
+            c3.live_n = nullptr; c3.t_span = nullptr;     // (the span is phase 2's here)
+            k_lin_seqw<<<waves_w, 64, SEQW_LDS, st>>>(c3);
+            HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(hipEventRecord(ctx->ev[EV_SEQ_END], st));
+        HIP_TRY(hipStreamWaitEvent(st, ctx->ev[EV_BFS_END], 0));
+        if (n_help > 0) HIP_TRY(hipStreamWaitEvent(st, ctx->ev[EV_HELP_END], 0));
+    } else {
+        HIP_TRY(hipEventRecord(ctx->ev[EV_P3_START], st));
+        HIP_TRY(hipEventRecord(ctx->ev[EV_SEQ_END], st));
+    }
+    entry_lists(/*live=*/true);
+}
+
+// Phase 3's launch. Few keys (no more than phase 2's CUs): a lone wave and the
+// 128 KB LDS memo each, as in phase 2; more: four waves per CU. Both kernels
+// are launched and the count phase 2 left on the device picks one.
+void LinRun::launch_phase3_lean(int waves, hipStream_t s) {
+    const DfsArgs c3 = phase3_lean_args();
+    const int few = std::max(1, ctx->n_cu - wg2);
+    DfsArgs c3a = c3;
+    c3a.queue = q + Q_P3_QUEUE_FEW; c3a.n_max = few;
+    k_lin_seq<true><<<std::min(waves, few), 64, MemoH::LDS, s>>>(c3a);
+    HIP_TRY(hipGetLastError());
+    DfsArgs c3b = c3;
+    c3b.queue = q + Q_P3_QUEUE; c3b.n_min = few + 1;
+    k_lin_seq3<true><<<waves, 64, MemoM::LDS, s>>>(c3b);
+    HIP_TRY(hipGetLastError());
+}
+
+// Phase 1 on st -- or, without one, the heavy lists it would have left: a
+// configurations request's keys, or every key that needs a search (:linear,
+// stage 2 of a two-stage check). Then the counters, the sorted heavy lists
+// and the entry counts.
+// writes: qh, n_defer, n_def_l, n_def_w, n_x, a.prio_ins
+void LinRun::run_phase1() {
+    HIP_TRY(hipEventRecord(ctx->ev[EV_P1_START], st));
+    if (!linear_mode && !skip_p1) {
+        k_lin_dfs<true, false><<<waves1, 64, MemoQ::LDS, st>>>(a);
+        HIP_TRY(hipGetLastError());
+        k_lin_dfs<false, false><<<std::min(waves1, 1024), 64, MemoQ::LDS, st>>>(phase1_wide_args());
+        a.prio_ins = 0;                       // the heavy-key passes inherit a: no priorities there
+    } else if (cfgreq) {
+        k_req_lists<<<1, 1, 0, st>>>(cfgreq->keys_dev, cfgreq->n_q, K, defer, defer_l, q);
+    } else {
+        // :linear, or stage 2 of a two-stage check: every key that needs a
+        // search is a heavy key
+        k_linear_lists<<<1, 1024, 0, st>>>(list, q + Q_N_LIST, list_w, q + Q_N_LIST_W, defer, defer_l, defer_w, q);
+    }
+    a.prio_ins = 0;
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ctx->ev[EV_P1_END], st));
+    HIP_TRY(hipMemcpyAsync(qh, q, sizeof qh, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    n_defer = qh[Q_DEFER]; n_def_l = qh[Q_DEFER_L]; n_def_w = qh[Q_DEFER_W];
+    n_x = cfgreq ? 0 : qh[Q_N_LIST_X];
+    if (n_def_l + n_def_w != n_defer) throw_jh(JH_EDEVICE, "deferred-key lists disagree");
+    if (n_defer > 0 && !linear_mode && !skip_p1) sort_deferred();
+    if (n_defer > 0 || n_x > 0) entry_lists(/*live=*/false);
+    diag_phase1_waves();
+}
+
+// heavy keys, heaviest estimate first (the likely longest searches start
+// first), sorted on the device: no host round trip between the phases
+// (stage 1 of a two-stage check reads the list too: k_mark_deferred)
+void LinRun::sort_deferred() {
+    SortLists sl{};
+    const int nn[3] = {n_defer, n_def_l, n_def_w};
+    int32_t *outs[3] = {defer, defer_l, defer_w};
+    for (int i = 0; i < 3; i++) { sl.in[i] = d64 + (size_t)i * (K + 1); sl.out[i] = outs[i]; sl.n[i] = nn[i]; }
+    k_sort_defer<<<3, 1024, 0, st>>>(sl);
+    for (int i = 0; i < 3; i++) {
+        if (nn[i] <= SORT_SMALL) continue;
+        uint64_t *tk = ctx->ws<uint64_t>(WS_DEFER64_T, (size_t)K + 1);
+        size_t tbs = 0;
+        HIP_TRY(hipcub::DeviceRadixSort::SortKeys(nullptr, tbs, sl.in[i], tk, nn[i], 0, 64, st));
+        HIP_TRY(hipcub::DeviceRadixSort::SortKeys(ctx->ws<char>(WS_LTMP, tbs), tbs, sl.in[i], tk, nn[i], 0, 64, st));
+        k_unpack_keys<<<grid_for(nn[i], 256), 256, 0, st>>>(tk, nn[i], outs[i]);
+    }
+}
+
+// Stage 1 of a two-stage check: the heavy keys come back unsearched, for the
+// pool: the deferred ones with their quick search's progress, the
+// 65-256-member ones (heavy keys too) with progress 0
+// writes: n_x
+void LinRun::run_stage1() {
+    if (n_x > 0) {
+        k_mark_list_deferred<<<grid_for(n_x, 256), 256, 0, st>>>(list_x, n_x, out_dev);
+        HIP_TRY(hipGetLastError());
+        n_x = 0;
+    }
+    if (n_defer > 0) k_mark_deferred<<<grid_for(n_defer, 256), 256, 0, st>>>(d64, n_defer, out_dev);
+    record_no_heavy_keys();
+}
+
+// windows wider than 64: k_lin_xw on the third stream, alongside phases 2 and 3
+// writes: prep_xw's; xa.t_span
+void LinRun::launch_xw() {
+    if (n_x <= 0) return;
+    prep_xw(qh);
+    xa.t_span = nullptr;
+    HIP_TRY(hipEventRecord(ctx->ev[EV_XW_START], st));
+    HIP_TRY(hipStreamWaitEvent(ctx->aux2, ctx->ev[EV_XW_START], 0));
+    k_lin_xw<<<waves_x, 64, 0, ctx->aux2>>>(xa);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ctx->ev[EV_XW_END], ctx->aux2));
+}
+
+// JH_WG=1 (tuning builds): deferred LEAN keys on k_lin_wg (one workgroup per
+// key, stream st), WIDE keys on the aux stream
+// writes: build_wg's and prep_wide's
+void LinRun::run_wg_mode() {
+    HIP_TRY(hipMemsetAsync(q + Q_QUEUE, 0, sizeof(int32_t), st));
+    WgArgs wa{};
+    if (n_def_l > 0) wa = build_wg(ctx->n_cu, nullptr, q + Q_QUEUE);
+    prep_wide();
+    HIP_TRY(hipEventRecord(ctx->ev[EV_FORK], st));
+    HIP_TRY(hipEventRecord(ctx->ev[EV_WG_START], st));
+    if (n_def_l > 0) {
+        k_lin_wg<<<n_wg, WG_THREADS, WG_LDS, st>>>(wa);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipEventRecord(ctx->ev[EV_BFS_END], st));
+    HIP_TRY(hipStreamWaitEvent(ctx->aux, ctx->ev[EV_FORK], 0));
+    HIP_TRY(hipEventRecord(ctx->ev[EV_P2_END], ctx->aux));
+    launch_wide(ctx->aux, true);
+    HIP_TRY(hipEventRecord(ctx->ev[EV_SEQ_END], ctx->aux));
+}
+
+// :algorithm :linear (checker.clj:141-145): the reachable-set search
+// (k_lin_bfs in linear mode) is the analysis for every key it can hold
+// -- JIT linearization's configuration sets, layer by layer -- on every
+// CU; the keys it cannot (windows over 32 members, >= 4096 states, more
+// than budget + 1 configurations) are decided by WGL afterwards on the
+// same stream, and k_frontier reports each key's analyzer.
+// A configurations request (cfgreq) runs here too: the BFS stops at the last
+// layer and dumps it, and k_lin_xw takes the keys the BFS cannot hold.
+// writes: claim, wg2, c, waves2, n_x, and prep_xw's for a configurations request
+void LinRun::run_linear() {
+    claim = ctx->ws<int32_t>(WS_CLAIM, K);
+    HIP_TRY(hipMemsetAsync(claim, 0, (size_t)K * sizeof(int32_t), st));
+    HIP_TRY(hipMemsetAsync(q + Q_QUEUE, 0, sizeof(int32_t), st));
+    HIP_TRY(hipMemsetAsync(q + Q_UNRES, 0, sizeof(int32_t), st));
+    HIP_TRY(hipMemsetAsync(q + Q_P2_QUEUE, 0, 2 * sizeof(int32_t), st));     // and Q_WIDE_QUEUE
+    const int64_t reach_cap = budget + 1;
+    // no WGL count, nothing to store -- except for a configurations request,
+    // which needs the last layer reached: every node
+    const uint32_t ncap = cfgreq ? (uint32_t)std::min<int64_t>(reach_cap + 64, (int64_t)1 << 30) : 1u << 16;
+    const BfsSizes sz = bfs_table_sizes(reach_cap);
+    const uint32_t set_cap = sz.set_cap, q_cap = sz.q_cap;
+    const uint32_t lcap = (uint32_t)smax + 2;
+    const uint64_t per_bfs = (uint64_t)set_cap * 8 + 4ULL * q_cap * 8 + scr_bytes_bfs + (uint64_t)ncap * 8 +
+                             (uint64_t)lcap * 4;
+    wg2 = fit_units(ctx, std::min(n_defer, ctx->n_cu), per_bfs, {WS_BFS_SET, WS_BFS_Q, WS_BFS_NODES});
+    c = BfsArgs{};
+    c.src = key_src();
+    c.list = defer; c.n_list = n_defer; c.queue = q + Q_QUEUE; c.out = out_dev;
+    c.unres_list = ctx->ws<int32_t>(WS_BFS_META, n_defer + 1); c.unres_count = q + Q_UNRES;
+    c.gset = ctx->ws<uint64_t>(WS_BFS_SET, (size_t)wg2 * set_cap); c.gset_cap = set_cap;
+    uint64_t *bq = ctx->ws<uint64_t>(WS_BFS_Q, (size_t)wg2 * 4 * q_cap);
+    c.pend = bq; c.front = bq + (size_t)wg2 * 2 * q_cap; c.q_cap = q_cap;
+    c.scratch = ctx->ws<char>(WS_SCRATCH_BFS, (size_t)wg2 * scr_bytes_bfs); c.scratch_bytes = scr_bytes_bfs;
+    c.budget = budget; c.init_state = init_state; c.states_ok = n_states < 4096 ? 1 : 0;
+    c.claim = claim; c.reach_cap = reach_cap; c.linear = 1;
+    c.ncap = ncap; c.hcap = 1u << 17; c.lcap = lcap;
+    if (cfgreq) {
+        c.cfg_slot = cfgreq->slot_dev; c.cfg_out = cfgreq->out_dev; c.cfg_n = cfgreq->n_dev;
+        c.cfg_rows = cfgreq->rows_dev; c.cfg_per = cfgreq->per_key;
+        c.col_val = dh->value; c.col_val2 = dh->value2;
+        c.vmin = vmin; c.init_value = init; c.per_key_values = per_key_values ? 1 : 0;
+    }
+    c.nodes = ctx->ws<uint64_t>(WS_BFS_NODES, (size_t)wg2 * ncap);
+    c.lstart = ctx->ws<uint32_t>(WS_BFS_LSTART, (size_t)wg2 * lcap);
+    ensure_lds_attrs();
+    // WGL for what the analysis cannot hold: LEAN and WIDE kernels over the
+    // unresolved list (each takes its own kind), after the BFS
+    const int want_f = std::min(n_defer, 4 * ctx->n_cu);
+    const uint64_t per_f = (uint64_t)cap2 * 16 + (uint64_t)stack_cap * sizeof(Frame) + scr_bytes_h;
+    waves2 = fit_units(ctx, want_f, per_f, {WS_MEMO_DEEP, WS_STACK_DEEP, WS_SCRATCH_DEEP});
+    const bool fresh2 = ctx->ws_fresh(WS_MEMO_DEEP) || ctx->bufs[WS_MEMO_DEEP].bytes < (size_t)waves2 * cap2 * 16;
+    uint64_t *memo2 = ctx->ws<uint64_t>(WS_MEMO_DEEP, (size_t)waves2 * cap2 * 2, /*zero=*/true);
+    if (clear_memo && !fresh2) HIP_TRY(hipMemsetAsync(memo2, 0, ctx->bufs[WS_MEMO_DEEP].bytes, st));
+    DfsArgs f = a;
+    f.handover_min = 0;
+    f.rs_mode = 0;
+    f.list = c.unres_list; f.n_list = 0; f.n_list_dev = q + Q_UNRES; f.queue = q + Q_P2_QUEUE; f.defer = 0;
+    f.defer_list = nullptr; f.defer_count = nullptr;
+    f.defer64 = nullptr; f.defer_kind = nullptr; f.defer_kind_count = nullptr;
+    f.memo = memo2; f.memo_cap = cap2;
+    f.stack = ctx->ws<Frame>(WS_STACK_DEEP, (size_t)waves2 * stack_cap);
+    f.scratch = ctx->ws<char>(WS_SCRATCH_DEEP, (size_t)waves2 * scr_bytes_h); f.scratch_bytes = scr_bytes_h;
+    f.budget = budget; f.budget_full = 0; f.claim = nullptr;
+    f.gen_base = ctx->gen_base + (uint32_t)K + 1;
+    f.probes = (unsigned long long *)(q + Q_PROBES_SEQ); f.dbg = nullptr; f.defer_time = nullptr;
+    f.seq_start = nullptr; f.exit_count = nullptr; f.cause_or = CAUSE_BY_WGL;
+    HIP_TRY(hipEventRecord(ctx->ev[EV_FORK], st));
+    k_lin_bfs<<<wg2, BFS_THREADS, BFS_LDS_BYTES, st>>>(c);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ctx->ev[EV_BFS_END], st));
+    if (!cfgreq) {
+        k_lin_seq3<true><<<waves2, 64, MemoM::LDS, st>>>(f);
+        HIP_TRY(hipGetLastError());
+        DfsArgs fw = f;
+        fw.queue = q + Q_WIDE_QUEUE;
+        k_lin_seqw<<<waves2, 64, SEQW_LDS, st>>>(fw);
+        HIP_TRY(hipGetLastError());
+    } else {
+        // configurations of the requested keys the reachable-set
+        // engine cannot hold (windows over 32 members, >= 4096 states):
+        // the 65-256-member search (4-word masks, every configuration
+        // in its table, any window up to JH_MAX_WINDOW) and the
+        // frontier from its table (xw_dump_configs)
+        HIP_TRY(hipMemsetAsync(q + Q_XW_MAX, 0, 2 * sizeof(int32_t), st));
+        k_xw_need<<<grid_for(n_defer, 256), 256, 0, st>>>(c.unres_list, q + Q_UNRES, meta,
+                                                         (unsigned long long *)(q + Q_XW_MAX));
+        int32_t qx[Q_WORDS];
+        HIP_TRY(hipMemcpyAsync(qx, q, sizeof qx, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        n_x = qx[Q_UNRES];
         if (n_x > 0) {
-            prep_xw(qh);
-            xa.t_span = nullptr;
-            HIP_TRY(hipEventRecord(ctx->ev[8], st));
-            HIP_TRY(hipStreamWaitEvent(ctx->aux2, ctx->ev[8], 0));
-            k_lin_xw<<<waves_x, 64, 0, ctx->aux2>>>(xa);
+            prep_xw(qx);
+            xa.list = c.unres_list; xa.n_list = n_x; xa.t_span = nullptr;
+            xa.cfg_slot = cfgreq->slot_dev; xa.cfg_out = cfgreq->out_dev; xa.cfg_n = cfgreq->n_dev;
+            xa.cfg_rows = cfgreq->rows_dev; xa.cfg_per = cfgreq->per_key;
+            xa.col_val = dh->value; xa.col_val2 = dh->value2;
+            xa.vmin = vmin; xa.init_value = init; xa.per_key_values = per_key_values ? 1 : 0;
+            k_lin_xw<<<waves_x, 64, 0, st>>>(xa);
             HIP_TRY(hipGetLastError());
-            HIP_TRY(hipEventRecord(ctx->ev[9], ctx->aux2));
         }
-        if (n_defer > 0 && p1_only) {
-            // stage 1 of a two-stage check: the deferred keys come back unsearched
-            k_mark_deferred<<<grid_for(n_defer, 256), 256, 0, st>>>(d64, n_defer, out_dev);
-            HIP_TRY(hipEventRecord(ctx->ev[6], st));
-            HIP_TRY(hipEventRecord(ctx->ev[5], st));
-            HIP_TRY(hipEventRecord(ctx->ev[10], st));
-            HIP_TRY(hipEventRecord(ctx->ev[7], st));
-        } else if (n_defer > 0 && use_wg) {
-            // Deferred LEAN keys on k_lin_wg (one workgroup per key, stream st),
-            // WIDE keys on the aux stream
-            HIP_TRY(hipMemsetAsync(q, 0, sizeof(int32_t), st));
-            WgArgs wa{};
-            if (n_def_l > 0) wa = build_wg(ctx->n_cu, nullptr, q);
-            prep_wide();
-            HIP_TRY(hipEventRecord(ctx->ev[6], st));
-            HIP_TRY(hipEventRecord(ctx->ev[11], st));
-            if (n_def_l > 0) {
-                k_lin_wg<<<n_wg, WG_THREADS, WG_LDS, st>>>(wa);
-                HIP_TRY(hipGetLastError());
-            }
-            HIP_TRY(hipEventRecord(ctx->ev[5], st));
-            HIP_TRY(hipStreamWaitEvent(ctx->aux, ctx->ev[6], 0));
-            HIP_TRY(hipEventRecord(ctx->ev[10], ctx->aux));
-            launch_wide(ctx->aux, true);
-            HIP_TRY(hipEventRecord(ctx->ev[7], ctx->aux));
-        } else if (n_defer > 0 && linear_mode) {
-            // :algorithm :linear (checker.clj:141-145): the reachable-set search
-            // (k_lin_bfs in linear mode) is the analysis for every key it can hold
-            // -- JIT linearization's configuration sets, layer by layer -- on every
-            // CU; the keys it cannot (windows over 32 members, >= 4096 states, more
-            // than budget + 1 configurations) are decided by WGL afterwards on the
-            // same stream, and k_frontier reports each key's analyzer.
-            claim = ctx->ws<int32_t>(WS_CLAIM, K);
-            HIP_TRY(hipMemsetAsync(claim, 0, (size_t)K * sizeof(int32_t), st));
-            HIP_TRY(hipMemsetAsync(q, 0, sizeof(int32_t), st));
-            HIP_TRY(hipMemsetAsync(q + 3, 0, sizeof(int32_t), st));
-            HIP_TRY(hipMemsetAsync(q + 6, 0, 2 * sizeof(int32_t), st));
-            const int64_t reach_cap = budget + 1;
-            // no WGL count, nothing to store -- except for a configurations request,
-            // which needs the last layer reached: every node
-            const uint32_t ncap = cfgreq ? (uint32_t)std::min<int64_t>(reach_cap + 64, (int64_t)1 << 30) : 1u << 16;
-            uint32_t set_cap = 1u << 12;
-            while ((int64_t)set_cap < 2 * reach_cap && set_cap < (1u << 30)) set_cap <<= 1;
-            const uint32_t q_cap = (uint32_t)std::min<int64_t>(reach_cap + 64, (int64_t)1 << 30);
-            const uint32_t lcap = (uint32_t)smax + 2;
-            const uint64_t per_bfs = (uint64_t)set_cap * 8 + 4ULL * q_cap * 8 + scr_bytes_bfs + (uint64_t)ncap * 8 +
-                                     (uint64_t)lcap * 4;
-            wg2 = fit_units(ctx, std::min(n_defer, ctx->n_cu), per_bfs, {WS_BFS_SET, WS_BFS_Q, WS_BFS_NODES});
-            BfsArgs c{};
-            c.src = KeySrc{rec, pair, off, rB, viol, rank, q + 2};
-            c.list = defer; c.n_list = n_defer; c.queue = q; c.out = out_dev;
-            c.unres_list = ctx->ws<int32_t>(WS_BFS_META, n_defer + 1); c.unres_count = q + 3;
-            c.gset = ctx->ws<uint64_t>(WS_BFS_SET, (size_t)wg2 * set_cap); c.gset_cap = set_cap;
-            uint64_t *bq = ctx->ws<uint64_t>(WS_BFS_Q, (size_t)wg2 * 4 * q_cap);
-            c.pend = bq; c.front = bq + (size_t)wg2 * 2 * q_cap; c.q_cap = q_cap;
-            c.scratch = ctx->ws<char>(WS_SCRATCH_BFS, (size_t)wg2 * scr_bytes_bfs); c.scratch_bytes = scr_bytes_bfs;
-            c.budget = budget; c.init_state = init_state; c.states_ok = n_states < 4096 ? 1 : 0;
-            c.claim = claim; c.reach_cap = reach_cap; c.linear = 1;
-            c.ncap = ncap; c.hcap = 1u << 17; c.lcap = lcap;
-            if (cfgreq) {
-                c.cfg_slot = cfgreq->slot_dev; c.cfg_out = cfgreq->out_dev; c.cfg_n = cfgreq->n_dev;
-                c.cfg_rows = cfgreq->rows_dev; c.cfg_per = cfgreq->per_key;
-                c.col_val = dh->value; c.col_val2 = dh->value2;
-                c.vmin = vmin; c.init_value = init; c.per_key_values = per_key_values ? 1 : 0;
-            }
-            c.nodes = ctx->ws<uint64_t>(WS_BFS_NODES, (size_t)wg2 * ncap);
-            c.lstart = ctx->ws<uint32_t>(WS_BFS_LSTART, (size_t)wg2 * lcap);
-            if (!ctx->lds_attr) {
-                HIP_TRY(hipFuncSetAttribute((const void *)k_lin_bfs, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            BFS_LDS_BYTES));
-                HIP_TRY(hipFuncSetAttribute((const void *)k_lin_seq<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            MemoH::LDS));
-                HIP_TRY(hipFuncSetAttribute((const void *)k_lin_seq<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            MemoH::LDS));
-                ctx->lds_attr = true;
-            }
-            // WGL for what the analysis cannot hold: LEAN and WIDE kernels over the
-            // unresolved list (each takes its own kind), after the BFS
-            const int want_f = std::min(n_defer, 4 * ctx->n_cu);
-            const uint64_t per_f = (uint64_t)cap2 * 16 + (uint64_t)stack_cap * sizeof(Frame) + scr_bytes_h;
-            waves2 = fit_units(ctx, want_f, per_f, {WS_MEMO_DEEP, WS_STACK_DEEP, WS_SCRATCH_DEEP});
-            const bool fresh2 = ctx->ws_fresh(WS_MEMO_DEEP) || ctx->bufs[WS_MEMO_DEEP].bytes < (size_t)waves2 * cap2 * 16;
-            uint64_t *memo2 = ctx->ws<uint64_t>(WS_MEMO_DEEP, (size_t)waves2 * cap2 * 2, /*zero=*/true);
-            if (clear_memo && !fresh2) HIP_TRY(hipMemsetAsync(memo2, 0, ctx->bufs[WS_MEMO_DEEP].bytes, st));
-            DfsArgs f = a;
-            f.handover_min = 0;
-            f.rs_mode = 0;
-            f.list = c.unres_list; f.n_list = 0; f.n_list_dev = q + 3; f.queue = q + 6; f.defer = 0;
-            f.defer_list = nullptr; f.defer_count = nullptr;
-            f.defer64 = nullptr; f.defer_kind = nullptr; f.defer_kind_count = nullptr;
-            f.memo = memo2; f.memo_cap = cap2;
-            f.stack = ctx->ws<Frame>(WS_STACK_DEEP, (size_t)waves2 * stack_cap);
-            f.scratch = ctx->ws<char>(WS_SCRATCH_DEEP, (size_t)waves2 * scr_bytes_h); f.scratch_bytes = scr_bytes_h;
-            f.budget = budget; f.budget_full = 0; f.claim = nullptr;
-            f.gen_base = ctx->gen_base + (uint32_t)K + 1;
-            f.probes = (unsigned long long *)(q + 8); f.dbg = nullptr; f.defer_time = nullptr;
-            f.seq_start = nullptr; f.exit_count = nullptr; f.cause_or = CAUSE_BY_WGL;
-            HIP_TRY(hipEventRecord(ctx->ev[6], st));
-            k_lin_bfs<<<wg2, BFS_THREADS, BFS_LDS_BYTES, st>>>(c);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipEventRecord(ctx->ev[5], st));
-            if (!cfgreq) {
-                k_lin_seq3<true><<<waves2, 64, MemoM::LDS, st>>>(f);
-                HIP_TRY(hipGetLastError());
-                DfsArgs fw = f;
-                fw.queue = q + 7;
-                k_lin_seqw<<<waves2, 64, SEQW_LDS, st>>>(fw);
-                HIP_TRY(hipGetLastError());
-            } else {
-                // configurations of the requested keys the reachable-set
-                // engine cannot hold (windows over 32 members, >= 4096 states):
-                // the 65-256-member search (4-word masks, every configuration
-                // in its table, any window up to JH_MAX_WINDOW) and the
-                // frontier from its table (xw_dump_configs)
-                HIP_TRY(hipMemsetAsync(q + 26, 0, 2 * sizeof(int32_t), st));
-                k_xw_need<<<grid_for(n_defer, 256), 256, 0, st>>>(c.unres_list, q + 3, meta,
-                                                                 (unsigned long long *)(q + 26));
-                int32_t qx[Q_WORDS];
-                HIP_TRY(hipMemcpyAsync(qx, q, sizeof qx, hipMemcpyDeviceToHost, st));
-                HIP_TRY(hipStreamSynchronize(st));
-                n_x = qx[3];
-                if (n_x > 0) {
-                    prep_xw(qx);
-                    xa.list = c.unres_list; xa.n_list = n_x; xa.t_span = nullptr;
-                    xa.cfg_slot = cfgreq->slot_dev; xa.cfg_out = cfgreq->out_dev; xa.cfg_n = cfgreq->n_dev;
-                    xa.cfg_rows = cfgreq->rows_dev; xa.cfg_per = cfgreq->per_key;
-                    xa.col_val = dh->value; xa.col_val2 = dh->value2;
-                    xa.vmin = vmin; xa.init_value = init; xa.per_key_values = per_key_values ? 1 : 0;
-                    k_lin_xw<<<waves_x, 64, 0, st>>>(xa);
-                    HIP_TRY(hipGetLastError());
-                }
-                n_x = 0;
-            }
-            HIP_TRY(hipEventRecord(ctx->ev[10], st));
-            HIP_TRY(hipEventRecord(ctx->ev[7], st));
-        } else if (n_defer > 0) {
-            // Heavy keys: two exact searches race per key and the first to settle
-            // it writes its verdict (emit_verdict), the other abandons it.
-            //  - the workgroup BFS (stream st) settles keys with no reachable
-            //    terminal configuration (invalid) within the budget, and valid
-            //    keys whose reachable set it can store (WGL's exact count);
-            //  - the sequential search with the full budget (aux stream: LEAN
-            //    and WIDE keys in one grid) settles every key.
-            prep_race(n_defer, n_def_l);
-            if (resume) b.rs_mode = 2;      // (and phase 3, c3 = b: a record is replaced only by a takeover's newer one)
-            if (!resume) { b.handoff = nullptr; wh.d.handoff = nullptr; }   // (a takeover continues from records)
-            if (defer_times) {
-                // tuning builds: per key [BFS start, end, sequential start, end, helper start, end]
-                unsigned long long *tl = ctx->ws<unsigned long long>(WS_TL, TL_W * (size_t)K);
-                HIP_TRY(hipMemsetAsync(tl, 0, TL_W * sizeof(unsigned long long) * K, st));
-                c.tl = tl; b.tl = tl; bw.tl = tl;
-                if (n_help > 0) wh.d.tl = tl;
-            }
-
-            // the fork point: everything the phase-2 searches read (claims, queue
-            // counters, sorted lists, the cleared memo on a generation wrap) is
-            // ordered before it; every table of phases 2 and 3 is allocated above
-            // (an allocation after the fork would synchronise the device)
-            prep_wide();
-            HIP_TRY(hipEventRecord(ctx->ev[6], st));
-            // fork: the BFS on st, the LEAN and WIDE sequential searches on aux
-            // (one grid), helpers on aux3
-            HIP_TRY(hipStreamWaitEvent(ctx->aux, ctx->ev[6], 0));
-            k_lin_bfs<<<wg2, BFS_THREADS, BFS_LDS_BYTES, st>>>(c);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipEventRecord(ctx->ev[5], st));
-            bool wide_done = bfs_only;
-            if (bfs_only || (waves2 == 0 && waves_w == 0)) {}
-            else if (wg_race) { if (waves2) k_lin_wg<<<n_wg, WG_THREADS, WG_LDS, ctx->aux>>>(wr); }
-            else if (p2_m) {
-                DfsPair pr;
-                pr.l = b; pr.w = bw; pr.n_l = waves2;
-                pr.w.wave_off = waves2;
-                if (n_def_w > 0) k_lin_seq_lw<false, MemoM><<<waves2 + waves_w, 64, SEQLW_LDS, ctx->aux>>>(pr);
-                else if (p2_per_cu == P2_DENSE_PER_CU && p2_small_ok)
-                    k_lin_seq_lw<false, MemoP2D><<<waves2, 64, MemoP2D::LDS, ctx->aux>>>(pr);
-                else k_lin_seq_lw<false, MemoP2><<<waves2, 64, MemoP2::LDS, ctx->aux>>>(pr);
-                wide_done = true;
-            } else if (waves2) k_lin_seq<true><<<waves2, 64, MemoH::LDS, ctx->aux>>>(b);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipEventRecord(ctx->ev[10], ctx->aux));
-            if (!bfs_only) launch_wide(ctx->aux, !wide_done);
-            if (n_help > 0) {
-                // every helper leaves once the sequential search has left its
-                // queue (or after HELPER_MAX_TICKS): joined before the verdicts are read
-                HIP_TRY(hipStreamWaitEvent(ctx->aux3, ctx->ev[6], 0));
-                k_lin_wg<<<n_wg, WG_THREADS, WG_LDS, ctx->aux3>>>(wh);
-                HIP_TRY(hipGetLastError());
-                HIP_TRY(hipEventRecord(ctx->ev[12], ctx->aux3));
-            }
-            if (split3 && !bfs_only && !wg_race) {
-                // phase 3: the LEAN keys phase 2 handed over, full budget, on phase 2's
-                // tables (same stream, phase 2 has ended; a fresh generation range).
-                // Few of them (no more than phase 2's CUs): a lone wave and the 128 KB
-                // LDS memo each, as in phase 2; more: four waves per CU. Both kernels
-                // are launched and the count phase 2 left on the device picks one.
-                DfsArgs c3 = b;
-                c3.list = defer3; c3.n_list = 0; c3.n_list_dev = q + 16; c3.defer = 0;
-                c3.defer_list = nullptr; c3.defer_count = nullptr;
-                c3.seq_start = nullptr; c3.exit_count = nullptr; c3.stall = nullptr;
-                c3.budget = budget; c3.budget_full = 0; c3.handoff = nullptr;
-                c3.memo_cap = cap2;
-                c3.gen_base = ctx->gen_base + 2 * (uint32_t)K + 1;
-                c3.dbg = nullptr;
-                c3.probes = (unsigned long long *)(q + Q_PROBES_P3);
-                const int few = std::max(1, ctx->n_cu - wg2);
-                DfsArgs c3a = c3;
-                c3a.queue = q + 17; c3a.n_max = few;
-                k_lin_seq<true><<<std::min(waves3, few), 64, MemoH::LDS, ctx->aux>>>(c3a);
-                HIP_TRY(hipGetLastError());
-                DfsArgs c3b = c3;
-                c3b.queue = q + 18; c3b.n_min = few + 1;
-                k_lin_seq3<true><<<waves3, 64, MemoM::LDS, ctx->aux>>>(c3b);
-                HIP_TRY(hipGetLastError());
-            }
-            HIP_TRY(hipEventRecord(ctx->ev[7], ctx->aux));
-            HIP_TRY(hipStreamWaitEvent(st, ctx->ev[7], 0));
-            if (n_help > 0) HIP_TRY(hipStreamWaitEvent(st, ctx->ev[12], 0));
-            if (n_help > 0 && wh.key_prof) {
-                // JH_DEBUG=4: what the late helpers took (end time in us after their start)
-                HIP_TRY(hipStreamSynchronize(st));
-                std::vector<unsigned long long> kp(3 * (size_t)K);
-                HIP_TRY(hipMemcpy(kp.data(), wh.key_prof, kp.size() * 8, hipMemcpyDeviceToHost));
-                for (int64_t k = 0; k < K; k++)
-                    if (kp[3 * k])
-                        fprintf(stderr, "[jh-help] key %lld wg %llu verdict %llu won %llu inserts %llu cycles %llu end_us %llu\n",
-                                (long long)k, (kp[3 * k + 2] >> 8) & 0xFFF, kp[3 * k + 2] & 0xFF, (kp[3 * k + 2] >> 20) & 1,
-                                kp[3 * k + 1], kp[3 * k], kp[3 * k + 2] >> 32);
-            }
-            if (const char *dp = tune_env("JH_BFS_DUMP")) {
-                // debugging: workgroup 0's stored configurations (t:20 | s:12 | mask:32)
-                HIP_TRY(hipStreamSynchronize(st));
-                std::vector<uint64_t> nd(c.ncap);
-                HIP_TRY(hipMemcpy(nd.data(), c.nodes, nd.size() * 8, hipMemcpyDeviceToHost));
-                if (FILE *fp = fopen(dp, "wb")) { fwrite(nd.data(), 8, nd.size(), fp); fclose(fp); }
-            }
-            if (dbg2) {
-                HIP_TRY(hipMemcpyAsync(qh, q, sizeof qh, hipMemcpyDeviceToHost, st));
-                HIP_TRY(hipStreamSynchronize(st));
-                n_unres = qh[3];
-                std::vector<unsigned long long> h((size_t)wg2 * 16);
-                HIP_TRY(hipMemcpy(h.data(), dbg, h.size() * 8, hipMemcpyDeviceToHost));
-                for (int w = 0; w < wg2; w++)
-                    if (h[16 * w + 4])
-                        fprintf(stderr, "[jh-bfs] wg %d keys=%llu cycles=%llu rounds=%llu configs=%llu cyc/round=%.0f | "
-                                "count: hash=%llu live=%llu path=%llu closure=%llu cyc | global-set rounds=%llu cyc=%llu "
-                                "configs=%llu, LDS-set rounds cyc=%llu configs=%llu | live: layers=%llu (LDS %llu) head-cyc=%llu LDS-layers-cyc=%llu\n",
-                                w, h[16 * w + 4], h[16 * w], h[16 * w + 1], h[16 * w + 3],
-                                (double)h[16 * w] / std::max(1ULL, h[16 * w + 1]), h[16 * w + 5], h[16 * w + 6],
-                                h[16 * w + 7], h[16 * w + 8], h[16 * w + 10], h[16 * w + 9], h[16 * w + 11],
-                                h[16 * w + 12], h[16 * w + 13], h[16 * w + 14] & 0xFFFFFFFF, h[16 * w + 14] >> 32, h[16 * w + 15], h[16 * w + 2]);
-    #ifdef JH_BFS_PROF
-                {
-                    unsigned long long bp[8];
-                    HIP_TRY(hipMemcpyFromSymbol(bp, HIP_SYMBOL(g_bfs_prof), sizeof bp));
-                    const double nr = (double)std::max(1ULL, bp[4]), nl = (double)std::max(1ULL, bp[6]);
-                    unsigned long long bx[4];
-                    HIP_TRY(hipMemcpyFromSymbol(bx, HIP_SYMBOL(g_bfs_prof_x), sizeof bx));
-                    const double ni = (double)std::max(1ULL, bx[2]);
-                    fprintf(stderr, "[jh-bfs-prof] rounds=%llu cyc/round: claim+barrier %.0f items %.0f barrier %.0f tail %.0f | "
-                            "layers=%llu formation cyc/layer %.0f | tid0 items=%llu cyc/item: load+children %.0f insert8 %.0f record8 %.0f\n",
-                            bp[4], bp[0] / nr, bp[1] / nr, bp[2] / nr, bp[3] / nr, bp[6], bp[5] / nl, bx[2], bp[7] / ni, bx[0] / ni, bx[1] / ni);
-                    memset(bx, 0, sizeof bx);
-                    HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_bfs_prof_x), bx, sizeof bx));
-                    memset(bp, 0, sizeof bp);
-                    HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_bfs_prof), bp, sizeof bp));
-                }
-    #endif
-                std::vector<unsigned long long> g((size_t)waves2 * 16);
-                HIP_TRY(hipMemcpy(g.data(), dbg + 16 * 256, g.size() * 8, hipMemcpyDeviceToHost));
-                for (int w = 0; w < waves2; w++)
-                    if (g[16 * w + 4] > 0)
-                        fprintf(stderr, "[jh-seq] wave %d keys=%llu search=%llu cyc busy=%llu | steps=%llu inserts=%llu evict=%llu lay-loads=%llu op-loads=%llu spills=%llu refills=%llu slow=%llu hbm-probes=%llu | cyc/step=%.0f\n",
-                                w, g[16 * w + 3], g[16 * w + 2], g[16 * w + 9], g[16 * w + 4], g[16 * w + 5], g[16 * w + 6],
-                                g[16 * w + 7], g[16 * w + 10], g[16 * w + 11], g[16 * w + 12], g[16 * w + 13], g[16 * w + 14],
-                                (double)g[16 * w + 2] / std::max(1ULL, g[16 * w + 4]));
-            }
-        } else {
-            HIP_TRY(hipEventRecord(ctx->ev[6], st));
-            HIP_TRY(hipEventRecord(ctx->ev[5], st));
-            HIP_TRY(hipEventRecord(ctx->ev[10], st));
-            HIP_TRY(hipEventRecord(ctx->ev[7], st));
-        }
-        if (n_x > 0) HIP_TRY(hipStreamWaitEvent(st, ctx->ev[9], 0));
+        n_x = 0;
     }
-    HIP_TRY(hipEventRecord(ctx->ev[2], st));
-    if (defer_times && n_defer > 0) {
-        // timeline: when each deferred key was handed on (us after phase 1's
-        // first wave), when phase 1 ended, when the sequential search took the
-        // key (if helpers ran), and the key's final insert count
-        HIP_TRY(hipStreamSynchronize(st));
-        if (stream_p2) {
-            int32_t nd = 0;
-            HIP_TRY(hipMemcpy(&nd, q + 1, sizeof nd, hipMemcpyDeviceToHost));
-            n_defer = nd;
-        }
-        std::vector<unsigned long long> dt((size_t)K + 2);
-        HIP_TRY(hipMemcpy(dt.data(), a.defer_time, dt.size() * 8, hipMemcpyDeviceToHost));
-        std::vector<int32_t> dk(n_defer);
-        HIP_TRY(hipMemcpy(dk.data(), defer, sizeof(int32_t) * n_defer, hipMemcpyDeviceToHost));
-        std::vector<jh_key_verdict> vv(K);
-        HIP_TRY(hipMemcpy(vv.data(), out_dev, sizeof(jh_key_verdict) * K, hipMemcpyDeviceToHost));
-        std::vector<unsigned long long> ss;
-        if (ctx->bufs.size() > WS_HELP_START && ctx->bufs[WS_HELP_START].p) {
-            ss.resize(K);
-            HIP_TRY(hipMemcpy(ss.data(), ctx->bufs[WS_HELP_START].p, 8 * K, hipMemcpyDeviceToHost));
-        }
-        fprintf(stderr, "[jh-defer] phase 1: %.1f us (first wave start to last wave end)\n", (dt[1] - dt[0]) / 100.0);
-        std::vector<std::pair<double, int>> ev;
-        for (int d = 0; d < n_defer; d++) ev.push_back({(dt[2 + dk[d]] - dt[0]) / 100.0, dk[d]});
-        std::vector<std::pair<long long, int>> heavy;
-        for (int d = 0; d < n_defer; d++) heavy.push_back({vv[dk[d]].explored, dk[d]});
-        std::sort(heavy.rbegin(), heavy.rend());
-        std::vector<unsigned long long> tl;
-        if (ctx->bufs.size() > WS_TL && ctx->bufs[WS_TL].p) {
-            tl.resize(TL_W * (size_t)K);
-            HIP_TRY(hipMemcpy(tl.data(), ctx->bufs[WS_TL].p, 8 * tl.size(), hipMemcpyDeviceToHost));
-        }
-        auto us = [&](unsigned long long t) { return t ? (double)(t - dt[0]) / 100.0 : -1.0; };
-        for (int i = 0; i < std::min(n_defer, 12); i++) {
-            const int k = heavy[i].second;
-            double st_us = -1;
-            if (!ss.empty() && ss[k] && ss[k] != SEQ_HANDED) st_us = ((ss[k] & ~1ULL) - dt[0]) / 100.0;
-            fprintf(stderr, "[jh-defer] key %d explored %lld valid %d deferred %.1f us seq-start %.1f us", k,
-                    heavy[i].first, vv[k].valid, (dt[2 + k] - dt[0]) / 100.0, st_us);
-            if (!tl.empty())
-                fprintf(stderr, " | bfs %.1f-%.1f us seq %.1f-%.1f us", us(tl[TL_W * k]), us(tl[TL_W * k + 1]),
-                        us(tl[TL_W * k + 2]), us(tl[TL_W * k + 3]));
-            fprintf(stderr, "\n");
-        }
-        if (!tl.empty()) {
-            // the keys that ended last (the step's critical path)
-            std::vector<std::pair<unsigned long long, int>> last;
-            for (int d = 0; d < n_defer; d++) {
-                const int k = dk[d];
-                unsigned long long e = 0;
-                for (int w = 1; w < TL_W; w += 2) e = std::max(e, tl[TL_W * k + w]);
-                last.push_back({e, k});
-            }
-            std::sort(last.rbegin(), last.rend());
-            for (int i = 0; i < std::min(n_defer, 8); i++) {
-                const int k = last[i].second;
-                fprintf(stderr, "[jh-last] key %d explored %lld valid %d deferred %.1f | bfs %.1f-%.1f seq %.1f-%.1f help %.1f-%.1f us\n",
-                        k, (long long)vv[k].explored, vv[k].valid, (dt[2 + k] - dt[0]) / 100.0, us(tl[TL_W * k]),
-                        us(tl[TL_W * k + 1]), us(tl[TL_W * k + 2]), us(tl[TL_W * k + 3]), us(tl[TL_W * k + 4]),
-                        us(tl[TL_W * k + 5]));
-            }
-        }
-        if (const char *csv = tune_env("JH_TL_CSV")) {
-            // every deferred key: its quick search, its engines' times, its verdict
-            std::vector<unsigned long long> di(2 * (size_t)K);
-            HIP_TRY(hipMemcpy(di.data(), a.defer_info, 8 * di.size(), hipMemcpyDeviceToHost));
-            if (FILE *fo = fopen(csv, "a")) {
-                fprintf(fo, "key,explored,valid,deferred_us,p1_inserts,p1_tmax,n_ok,bfs0,bfs1,seq0,seq1,help0,help1\n");
-                for (int d = 0; d < n_defer; d++) {
-                    const int k = dk[d];
-                    fprintf(fo, "%d,%lld,%d,%.1f,%llu,%llu,%llu", k, (long long)vv[k].explored, vv[k].valid,
-                            (dt[2 + k] - dt[0]) / 100.0, di[2 * k], di[2 * k + 1] & 0xFFFFFFFFull, di[2 * k + 1] >> 32);
-                    for (int w = 0; w < TL_W; w++) fprintf(fo, ",%.1f", tl.empty() ? -1.0 : us(tl[TL_W * k + w]));
-                    fprintf(fo, "\n");
-                }
-                fclose(fo);
-            }
-        }
-        int q5[5] = {0, 0, 0, 0, 0};
-        for (auto &e2 : ev) q5[std::min(4, (int)(e2.first / (std::max(1.0, (dt[1] - dt[0]) / 100.0) / 5)))]++;
-        fprintf(stderr, "[jh-defer] deferrals by fifth of phase 1: %d %d %d %d %d\n", q5[0], q5[1], q5[2], q5[3], q5[4]);
-    }
-    ctx->gen_base += gen_span;
+    HIP_TRY(hipEventRecord(ctx->ev[EV_P2_END], st));
+    HIP_TRY(hipEventRecord(ctx->ev[EV_SEQ_END], st));
+}
 
-    k_fail_rows<<<(unsigned)std::min<int64_t>((K + 3) / 4, 4096), 256, 0, st>>>(
-        KeySrc{rec, pair, off, rB, viol, rank, q + 2}, out_dev, K);
-    k_frontier<<<(unsigned)std::min<int64_t>((K + 3) / 4, 4096), 256, 0, st>>>(
-        KeySrc{rec, pair, off, rB, viol, rank, q + 2}, out_dev, K, linear_mode ? 1 : 0);
+// The default schedule. Heavy keys: two exact searches race per key and the
+// first to settle it writes its verdict (emit_verdict), the other abandons it.
+//  - the workgroup BFS (stream st) settles keys with no reachable
+//    terminal configuration (invalid) within the budget, and valid
+//    keys whose reachable set it can store (WGL's exact count);
+//  - the sequential search with the full budget (aux stream: LEAN
+//    and WIDE keys in one grid) settles every key.
+// writes: prep_race's and prep_wide's; b.rs_mode, the handoff fields
+void LinRun::run_race() {
+    prep_race(n_defer, n_def_l);
+    if (resume) b.rs_mode = 2;      // (and phase 3, c3 = b: a record is replaced only by a takeover's newer one)
+    if (!resume) { b.handoff = nullptr; wh.d.handoff = nullptr; }   // (a takeover continues from records)
+    timeline_tables(/*wide=*/true);
+
+    // the fork point: everything the phase-2 searches read (claims, queue
+    // counters, sorted lists, the cleared memo on a generation wrap) is
+    // ordered before it; every table of phases 2 and 3 is allocated above
+    // (an allocation after the fork would synchronise the device)
+    prep_wide();
+    HIP_TRY(hipEventRecord(ctx->ev[EV_FORK], st));
+    // fork: the BFS on st, the LEAN and WIDE sequential searches on aux
+    // (one grid), helpers on aux3
+    HIP_TRY(hipStreamWaitEvent(ctx->aux, ctx->ev[EV_FORK], 0));
+    k_lin_bfs<<<wg2, BFS_THREADS, BFS_LDS_BYTES, st>>>(c);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ctx->ev[EV_BFS_END], st));
+    bool wide_done = bfs_only;
+    if (bfs_only || (waves2 == 0 && waves_w == 0)) {}
+    else if (wg_race) { if (waves2) k_lin_wg<<<n_wg, WG_THREADS, WG_LDS, ctx->aux>>>(wr); }
+    else if (p2_m) {
+        DfsPair pr;
+        pr.l = b; pr.w = bw; pr.n_l = waves2;
+        pr.w.wave_off = waves2;
+        if (n_def_w > 0) k_lin_seq_lw<false, MemoM><<<waves2 + waves_w, 64, SEQLW_LDS, ctx->aux>>>(pr);
+        else if (p2_per_cu == P2_DENSE_PER_CU && p2_small_ok)
+            k_lin_seq_lw<false, MemoP2D><<<waves2, 64, MemoP2D::LDS, ctx->aux>>>(pr);
+        else k_lin_seq_lw<false, MemoP2><<<waves2, 64, MemoP2::LDS, ctx->aux>>>(pr);
+        wide_done = true;
+    } else if (waves2) k_lin_seq<true><<<waves2, 64, MemoH::LDS, ctx->aux>>>(b);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ctx->ev[EV_P2_END], ctx->aux));
+    if (!bfs_only) launch_wide(ctx->aux, !wide_done);
+    if (n_help > 0) {
+        // every helper leaves once the sequential search has left its
+        // queue (or after HELPER_MAX_TICKS): joined before the verdicts are read
+        HIP_TRY(hipStreamWaitEvent(ctx->aux3, ctx->ev[EV_FORK], 0));
+        k_lin_wg<<<n_wg, WG_THREADS, WG_LDS, ctx->aux3>>>(wh);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(ctx->ev[EV_HELP_END], ctx->aux3));
+    }
+    if (split3 && !bfs_only && !wg_race) launch_phase3_lean(waves3, ctx->aux);
+    HIP_TRY(hipEventRecord(ctx->ev[EV_SEQ_END], ctx->aux));
+    HIP_TRY(hipStreamWaitEvent(st, ctx->ev[EV_SEQ_END], 0));
+    if (n_help > 0) HIP_TRY(hipStreamWaitEvent(st, ctx->ev[EV_HELP_END], 0));
+    diag_helper_keys();
+    diag_bfs_dump();
+    diag_race_waves();
+}
+
+// ---------------------------------------------------------------------------
+// Results: failing rows, frontiers, the summary, the flags word.
+// writes: qh; after a streaming pass n_defer, n_def_l, n_def_w (the final lengths); *sum
+void LinRun::finish() {
+    k_fail_rows<<<(unsigned)std::min<int64_t>((K + 3) / 4, 4096), 256, 0, st>>>(key_src(), out_dev, K);
+    k_frontier<<<(unsigned)std::min<int64_t>((K + 3) / 4, 4096), 256, 0, st>>>(key_src(), out_dev, K, linear_mode ? 1 : 0);
     long long *sd = ctx->ws<long long>(WS_SUMMARY, 8);
     long long s_init[8] = {0, 0, 0, LLONG_MAX, 0, 0, 0, 0};
     HIP_TRY(hipMemcpyAsync(sd, s_init, sizeof s_init, hipMemcpyHostToDevice, st));
@@ -7983,191 +8080,145 @@ void lin_check_independent(jh_ctx *ctx, const jh_history *dh, const jh_lin_opts 
     long long sh[8];
     HIP_TRY(hipMemcpyAsync(sh, sd, sizeof sh, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(qh, q, sizeof qh, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipEventRecord(ctx->ev[3], st));
+    HIP_TRY(hipEventRecord(ctx->ev[EV_END], st));
     HIP_TRY(hipStreamSynchronize(st));
-    if (qh[2] & 2) throw_jh(JH_EDEVICE, "per-key table exceeded the scratch reservation");
-    if (qh[2] & 4) throw_jh(JH_EDEVICE, "DFS stack overflow");
-    if ((qh[2] & 0x1F0) && acc_stats && ctx->bufs.size() > WS_DEBUG_WG && ctx->bufs[WS_DEBUG_WG].p && n_wg > 0 &&
-        dbgenv && atoi(dbgenv) >= 3) {
-        std::vector<unsigned long long> tr((size_t)n_wg * 256);
-        HIP_TRY(hipMemcpy(tr.data(), ctx->bufs[WS_DEBUG_WG].p, tr.size() * 8, hipMemcpyDeviceToHost));
-        for (int g = 0; g < n_wg; g++) {
-            for (int e = 0; e < 31; e++) {
-                const unsigned long long *d8 = &tr[(size_t)g * 256 + 8 * e];
-                if (!d8[3]) break;
-                fprintf(stderr, "[jh-acc] wg %d key %llu d %llu depth %llu roots %llu cap %llu status %llu tail %llu ins %llu\n",
-                        g, d8[0], d8[1], d8[2], d8[3], d8[4], d8[5], d8[6], d8[7]);
-            }
-            const unsigned long long *w8 = &tr[(size_t)g * 256 + 248];
-            if (w8[6] == 0xDEAD)
-                fprintf(stderr, "[jh-acc] wg %d WATCHDOG head %llu tail %llu active %llu cap_total %llu roots %llu wave %llu\n",
-                        g, w8[0], w8[1], w8[2], w8[3], w8[4], w8[5]);
-            const unsigned long long *l8 = &tr[(size_t)g * 256 + 240];
-            if (l8[3] == 0xBEEF)
-                fprintf(stderr, "[jh-acc] wg %d LOST ITEM pos %llu tail %llu cap_total %llu\n", g, l8[0], l8[1], l8[2]);
-        }
-    }
-    if (qh[2] & 0x3F0) {
+    if (qh[Q_FLAGS] & QF_TABLE_OVERFLOW) throw_jh(JH_EDEVICE, "per-key table exceeded the scratch reservation");
+    if (qh[Q_FLAGS] & QF_STACK_OVERFLOW) throw_jh(JH_EDEVICE, "DFS stack overflow");
+    diag_acc_trace();
+    if (qh[Q_FLAGS] & QF_WATCHDOGS) {
         char m[192];
         snprintf(m, sizeof m, "search watchdog tripped (flags 0x%x: 16 lost work item, 32 idle enumeration, "
-                 "64 full set, 128 step limit, 256 bad window, 512 stream wait)", qh[2]);
+                 "64 full set, 128 step limit, 256 bad window, 512 stream wait)", qh[Q_FLAGS]);
         throw_jh(JH_EDEVICE, m);
     }
     if (stream_p2) {
         // the live lists' final lengths (the bounds used to size the pass above)
-        n_defer = qh[1]; n_def_l = qh[Q_DEFER_L]; n_def_w = qh[Q_DEFER_W];
+        n_defer = qh[Q_DEFER]; n_def_l = qh[Q_DEFER_L]; n_def_w = qh[Q_DEFER_W];
         if (n_def_l + n_def_w != n_defer) throw_jh(JH_EDEVICE, "deferred-key lists disagree");
     }
-    if (tune_env("JH_WS_REPORT")) {
-        // tuning builds: the context's workspace, largest buffers first
-        std::vector<std::pair<size_t, int>> b;
-        size_t tot = 0;
-        for (int i = 0; i < (int)ctx->bufs.size(); i++) { b.push_back({ctx->bufs[i].bytes, i}); tot += ctx->bufs[i].bytes; }
-        std::sort(b.rbegin(), b.rend());
-        fprintf(stderr, "[jh-ws] total %.2f GB:", tot / 1073741824.0);
-        for (size_t i = 0; i < b.size() && i < 12; i++) fprintf(stderr, " slot %d %.2f GB;", b[i].second, b[i].first / 1073741824.0);
-        fprintf(stderr, "\n");
-    }
+    diag_ws_report();
     if (sum) {
-        sum->valid = sh[0]; sum->n_invalid = sh[1]; sum->n_unknown = sh[2];
-        sum->first_fail_entry = sh[3] == LLONG_MAX ? -1 : sh[3];
-        sum->n_keys = sh[4]; sum->explored = sh[5];
-        sum->memo_probes = q64(qh, 4);
-        float ms = 0, ms_dfs = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[3]));
-        HIP_TRY(hipEventElapsedTime(&ms_dfs, ctx->ev[1], ctx->ev[4]));
-        sum->device_ms = ms; sum->dfs_ms = ms_dfs;
-        sum->n_deferred = n_defer;
-        sum->deferred_entries = q64(qh, Q_ENT_ALL);
-        sum->seq_probes = q64(qh, 8);
-        sum->seq_ms = 0; sum->bfs_ms = 0; sum->p3_ms = 0; sum->wide_ms = 0; sum->xw_ms = 0;
-        sum->streamed = stream_p2 ? 1 : 0;
-        sum->p3_entries = q64(qh, Q_ENT_P3);
-        sum->p2_start_ms = -1; sum->p1_span_ms = 0;
-        sum->resumed = resume ? qh[Q_RS_USED + 2] : 0;
-        sum->takeovers = resume ? qh[Q_RS_USED + 3] : 0;
-        sum->spec_nodes = q64(qh, Q_SPEC); sum->spec_merges = qh[Q_SPEC + 2];
-        sum->spec_jobs = qh[Q_SPEC + 3]; sum->spec_dead = qh[Q_SPEC + 4];
-        sum->resume_bytes = resume ? q64(qh, Q_RS_USED) : 0;
-        // an engine's own span from its s_memrealtime words (100 MHz): [first key, last wave end]
-        auto span_ms = [&](int w) {
-            const int64_t t0 = q64(qh, w), t1 = q64(qh, w + 2);
-            return (t0 != -1 && t1 > t0) ? (t1 - t0) / 1e5 : 0.0;
-        };
-        if (stream_p2) {
-            sum->p1_span_ms = span_ms(Q_T_P1);
-            sum->seq_ms = span_ms(Q_T_LEAN);
-            sum->bfs_ms = span_ms(Q_T_BFS);
-            sum->xw_ms = span_ms(Q_T_XW);
-            if (waves_w > 0) sum->wide_ms = span_ms(Q_T_WIDE);
-            if (split3) { float c2 = 0; HIP_TRY(hipEventElapsedTime(&c2, ctx->ev[13], ctx->ev[7])); sum->p3_ms = c2; }
-            const int64_t p1s = q64(qh, Q_T_P1);
-            int64_t first = -1;
-            for (int w : {Q_T_BFS, Q_T_LEAN}) {
-                const int64_t t = q64(qh, w);
-                if (t != -1 && (first == -1 || t < first)) first = t;
-            }
-            if (first != -1 && p1s != -1) sum->p2_start_ms = (first - p1s) / 1e5;
-        } else if (n_defer > 0) {
-            float a2 = 0, b2 = 0;
-            if (use_wg) HIP_TRY(hipEventElapsedTime(&a2, ctx->ev[11], ctx->ev[5]));
-            else HIP_TRY(hipEventElapsedTime(&a2, ctx->ev[6], ctx->ev[10]));
-            sum->seq_ms = a2;
-            if (!use_wg) { HIP_TRY(hipEventElapsedTime(&b2, ctx->ev[6], ctx->ev[5])); sum->bfs_ms = b2; }
-            if (split3) { float c2 = 0; HIP_TRY(hipEventElapsedTime(&c2, ctx->ev[10], ctx->ev[7])); sum->p3_ms = c2; }
-            // the heavy-key pass's start (the fork), after phase 1's start
-            if (!use_wg && !p1_only) { float g2 = 0; HIP_TRY(hipEventElapsedTime(&g2, ctx->ev[1], ctx->ev[6])); sum->p2_start_ms = g2; }
-            // the WIDE waves' own span (they share a grid with the LEAN ones)
-            if (waves_w > 0 && q64(qh, Q_T_WIDE + 2) > q64(qh, Q_T_WIDE)) sum->wide_ms = (q64(qh, Q_T_WIDE + 2) - q64(qh, Q_T_WIDE)) / 1e5;
-        }
-        if (n_x > 0 && !stream_p2) { float e2 = 0; HIP_TRY(hipEventElapsedTime(&e2, ctx->ev[8], ctx->ev[9])); sum->xw_ms = e2; }
-#ifdef JH_XW_PROF
-        if (n_x > 0) {
-            unsigned long long x[12];
-            HIP_TRY(hipMemcpyFromSymbol(x, HIP_SYMBOL(g_xw_prof), sizeof x));
-            const double ni = (double)std::max(1ULL, x[5]);
-            fprintf(stderr, "[jh-xw-prof] keys=%llu inserts=%llu cyc/insert: search %.0f | probe %.0f (%.2f slice probes) "
-                    "push %.0f lift %.0f | layer loads %.2f x %.0f cyc | pops %.2f x %.0f cyc (HBM frames %llu)\n",
-                    x[11], x[5], x[0] / ni, x[1] / ni, x[6] / ni, x[4] / ni, x[9] / ni, x[7] / ni,
-                    x[2] / (double)std::max(1ULL, x[7]), x[8] / ni, x[3] / (double)std::max(1ULL, x[8]), x[10]);
-            memset(x, 0, sizeof x);
-            HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_xw_prof), x, sizeof x));
-        }
-#endif
-        sum->p3_probes = q64(qh, Q_PROBES_P3);
-        sum->wide_probes = q64(qh, Q_PROBES_WIDE);
-        sum->xw_probes = q64(qh, 22);
-        sum->helper_probes = q64(qh, Q_PROBES_HELP);
-        sum->n_deferred_wide = n_def_w;
-        sum->n_phase3 = split3 ? qh[16] : 0;
-        sum->n_phase3_wide = split3w ? qh[Q_DEFER3W] : 0;
-        sum->n_xw = n_x;
-        sum->lean_entries = q64(qh, Q_ENT_LEAN);
-        sum->wide_entries = q64(qh, Q_ENT_WIDE);
-        sum->xw_entries = q64(qh, Q_ENT_XW);
-        sum->waves[0] = waves2; sum->waves[1] = waves_w; sum->waves[2] = split3 ? waves3 : 0; sum->waves[3] = waves_x;
-        if (dbgenv) {
-            float a = 0, b = 0, c = 0;
-            HIP_TRY(hipEventElapsedTime(&a, ctx->ev[0], ctx->ev[1]));
-            HIP_TRY(hipEventElapsedTime(&b, ctx->ev[1], ctx->ev[4]));
-            float d = 0;
-            HIP_TRY(hipEventElapsedTime(&d, ctx->ev[4], ctx->ev[7]));
-            HIP_TRY(hipEventElapsedTime(&c, ctx->ev[4], ctx->ev[5]));
-            fprintf(stderr, "[jh] keys=%lld prep=%.3f ms phase1=%.3f ms (waves %d) deferred=%d (wide %d) bfs=%.3f ms (gave up %d) "
-                    "seq=%.3f ms (phase 2 %.3f ms, phase 3 %lld keys %.3f ms) wide %.3f ms (%d waves, phase 3 %lld keys) "
-                    "xw %d keys %.3f ms (%d waves)\n",
-                    (long long)K, a, b, waves1, n_defer, n_def_w, c, n_unres, d, sum->seq_ms, (long long)sum->n_phase3,
-                    sum->p3_ms, sum->wide_ms, waves_w, (long long)sum->n_phase3_wide, n_x, sum->xw_ms, waves_x);
-            if (acc_stats && dbgenv && atoi(dbgenv) >= 3 && n_wg > 0) {
-                std::vector<unsigned long long> tr((size_t)n_wg * 256);
-                HIP_TRY(hipMemcpy(tr.data(), ctx->bufs[WS_DEBUG_WG].p, tr.size() * 8, hipMemcpyDeviceToHost));
-                for (int g = 0; g < std::min(n_wg, 8); g++)
-                    for (int e = 0; e < 32; e++) {
-                        const unsigned long long *d8 = &tr[(size_t)g * 256 + 8 * e];
-                        if (!d8[3]) break;
-                        fprintf(stderr, "[jh-acc] wg %d key %llu d %llu depth %llu roots %llu cap %llu status %llu tail %llu ins %llu\n",
-                                g, d8[0], d8[1], d8[2], d8[3], d8[4], d8[5], d8[6], d8[7]);
-                    }
-            }
-            if (acc_stats && dbgenv && atoi(dbgenv) >= 4) {
-                std::vector<unsigned long long> kp(3 * (size_t)K);
-                HIP_TRY(hipMemcpy(kp.data(), ctx->bufs[WS_STATS_KEYS].p, kp.size() * 8, hipMemcpyDeviceToHost));
-                std::vector<int> ix;
-                for (int64_t k = 0; k < K; k++) if (kp[3 * k]) ix.push_back((int)k);
-                std::sort(ix.begin(), ix.end(), [&](int x, int y) { return kp[3 * x] > kp[3 * y]; });
-                for (size_t i = 0; i < std::min<size_t>(12, ix.size()); i++)
-                    fprintf(stderr, "[jh-key] key %d memtime %.3g inserts %llu verdict %llu wg %llu\n", ix[i],
-                            (double)kp[3 * ix[i]], kp[3 * ix[i] + 1], kp[3 * ix[i] + 2] & 255, kp[3 * ix[i] + 2] >> 8);
-            }
-#ifdef JH_ENUM_PROF
-            {
-                unsigned int a4[4]; unsigned long long b3[3];
-                HIP_TRY(hipMemcpyFromSymbol(a4, HIP_SYMBOL(g_prof_hbm), 4));
-                HIP_TRY(hipMemcpyFromSymbol(a4 + 1, HIP_SYMBOL(g_prof_gset), 4));
-                HIP_TRY(hipMemcpyFromSymbol(a4 + 2, HIP_SYMBOL(g_prof_rounds), 4));
-                HIP_TRY(hipMemcpyFromSymbol(a4 + 3, HIP_SYMBOL(g_prof_layers), 4));
-                HIP_TRY(hipMemcpyFromSymbol(b3, HIP_SYMBOL(g_prof_form), 8));
-                HIP_TRY(hipMemcpyFromSymbol(b3 + 1, HIP_SYMBOL(g_prof_close), 8));
-                fprintf(stderr, "[jh-prof] hbm-probes %u gset-inserts %u rounds %u layers %u | memtime formation %.3g closure %.3g\n",
-                        a4[0], a4[1], a4[2], a4[3], (double)b3[0], (double)b3[1]);
-                unsigned int z4[4] = {0, 0, 0, 0}; unsigned long long zb[3] = {0, 0, 0};
-                HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_prof_hbm), z4, 4));
-                HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_prof_gset), z4, 4));
-                HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_prof_rounds), z4, 4));
-                HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_prof_layers), z4, 4));
-                HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_prof_form), zb, 8));
-                HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_prof_close), zb, 8));
-            }
-#endif
-            if (acc_stats) {
-                unsigned long long st8[8];
-                HIP_TRY(hipMemcpy(st8, acc_stats, sizeof st8, hipMemcpyDeviceToHost));
-                fprintf(stderr, "[jh-wg] workgroups=%d enumerations=%llu new-nodes=%llu dead=%llu live=%llu inconclusive=%llu | "
-                        "memtime: keys %.3g, in enumerations %.3g (work loops %.3g)\n",
-                        n_wg, st8[0], st8[1], st8[2], st8[3], st8[4], (double)st8[7], (double)st8[5], (double)st8[6]);
-            }
-        }
+        fill_summary(sh);
+        diag_xw_prof();
+        diag_summary();
     }
+}
+
+// an engine's own span from its s_memrealtime words (100 MHz): [first key, last wave end]
+double span_ms(const int32_t *qh, int w) {
+    const int64_t t0 = q64(qh, w), t1 = q64(qh, w + Q_T_END);
+    return (t0 != -1 && t1 > t0) ? (t1 - t0) / 1e5 : 0.0;
+}
+
+void LinRun::fill_summary(const long long *sh) {
+    sum->valid = sh[0]; sum->n_invalid = sh[1]; sum->n_unknown = sh[2];
+    sum->first_fail_entry = sh[3] == LLONG_MAX ? -1 : sh[3];
+    sum->n_keys = sh[4]; sum->explored = sh[5];
+    sum->memo_probes = q64(qh, Q_PROBES_P1);
+    float ms = 0, ms_dfs = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, ctx->ev[EV_START], ctx->ev[EV_END]));
+    HIP_TRY(hipEventElapsedTime(&ms_dfs, ctx->ev[EV_P1_START], ctx->ev[EV_P1_END]));
+    sum->device_ms = ms; sum->dfs_ms = ms_dfs;
+    sum->n_deferred = n_defer;
+    sum->deferred_entries = q64(qh, Q_ENT_ALL);
+    sum->seq_probes = q64(qh, Q_PROBES_SEQ);
+    sum->seq_ms = 0; sum->bfs_ms = 0; sum->p3_ms = 0; sum->wide_ms = 0; sum->xw_ms = 0;
+    sum->streamed = stream_p2 ? 1 : 0;
+    sum->p3_entries = q64(qh, Q_ENT_P3);
+    sum->p2_start_ms = -1; sum->p1_span_ms = 0;
+    sum->resumed = resume ? qh[Q_RS_PUBLISHED] : 0;
+    sum->takeovers = resume ? qh[Q_RS_TAKEOVERS] : 0;
+    sum->spec_nodes = q64(qh, Q_SPEC); sum->spec_merges = qh[Q_SPEC_MERGES];
+    sum->spec_jobs = qh[Q_SPEC_JOBS]; sum->spec_dead = qh[Q_SPEC_DEAD];
+    sum->resume_bytes = resume ? q64(qh, Q_RS_USED) : 0;
+    if (stream_p2) {
+        sum->p1_span_ms = span_ms(qh, Q_T_P1);
+        sum->seq_ms = span_ms(qh, Q_T_LEAN);
+        sum->bfs_ms = span_ms(qh, Q_T_BFS);
+        sum->xw_ms = span_ms(qh, Q_T_XW);
+        if (waves_w > 0) sum->wide_ms = span_ms(qh, Q_T_WIDE);
+        if (split3) { float c2 = 0; HIP_TRY(hipEventElapsedTime(&c2, ctx->ev[EV_P3_START], ctx->ev[EV_SEQ_END])); sum->p3_ms = c2; }
+        const int64_t p1s = q64(qh, Q_T_P1);
+        int64_t first = -1;
+        for (int w : {Q_T_BFS, Q_T_LEAN}) {
+            const int64_t t = q64(qh, w);
+            if (t != -1 && (first == -1 || t < first)) first = t;
+        }
+        if (first != -1 && p1s != -1) sum->p2_start_ms = (first - p1s) / 1e5;
+    } else if (n_defer > 0) {
+        float a2 = 0, b2 = 0;
+        if (use_wg) HIP_TRY(hipEventElapsedTime(&a2, ctx->ev[EV_WG_START], ctx->ev[EV_BFS_END]));
+        else HIP_TRY(hipEventElapsedTime(&a2, ctx->ev[EV_FORK], ctx->ev[EV_P2_END]));
+        sum->seq_ms = a2;
+        if (!use_wg) { HIP_TRY(hipEventElapsedTime(&b2, ctx->ev[EV_FORK], ctx->ev[EV_BFS_END])); sum->bfs_ms = b2; }
+        if (split3) { float c2 = 0; HIP_TRY(hipEventElapsedTime(&c2, ctx->ev[EV_P2_END], ctx->ev[EV_SEQ_END])); sum->p3_ms = c2; }
+        // the heavy-key pass's start (the fork), after phase 1's start
+        if (!use_wg && !p1_only) { float g2 = 0; HIP_TRY(hipEventElapsedTime(&g2, ctx->ev[EV_P1_START], ctx->ev[EV_FORK])); sum->p2_start_ms = g2; }
+        // the WIDE waves' own span (they share a grid with the LEAN ones)
+        if (waves_w > 0 && q64(qh, Q_T_WIDE + Q_T_END) > q64(qh, Q_T_WIDE))
+            sum->wide_ms = (q64(qh, Q_T_WIDE + Q_T_END) - q64(qh, Q_T_WIDE)) / 1e5;
+    }
+    if (n_x > 0 && !stream_p2) { float e2 = 0; HIP_TRY(hipEventElapsedTime(&e2, ctx->ev[EV_XW_START], ctx->ev[EV_XW_END])); sum->xw_ms = e2; }
+    sum->p3_probes = q64(qh, Q_PROBES_P3);
+    sum->wide_probes = q64(qh, Q_PROBES_WIDE);
+    sum->xw_probes = q64(qh, Q_PROBES_XW);
+    sum->helper_probes = q64(qh, Q_PROBES_HELP);
+    sum->n_deferred_wide = n_def_w;
+    sum->n_phase3 = split3 ? qh[Q_DEFER3] : 0;
+    sum->n_phase3_wide = split3w ? qh[Q_DEFER3W] : 0;
+    sum->n_xw = n_x;
+    sum->lean_entries = q64(qh, Q_ENT_LEAN);
+    sum->wide_entries = q64(qh, Q_ENT_WIDE);
+    sum->xw_entries = q64(qh, Q_ENT_XW);
+    sum->waves[0] = waves2; sum->waves[1] = waves_w; sum->waves[2] = split3 ? waves3 : 0; sum->waves[3] = waves_x;
+}
+
+}  // namespace
+
+// The check: prepare the history, run phase 1 over every key, give the keys
+// it deferred to the schedule the options pick, collect the results.
+void lin_check_independent(jh_ctx *ctx, const jh_history *dh, const jh_lin_opts *opts,
+                           bool keyed, jh_key_verdict *out_dev, jh_summary *sum,
+                           hipStream_t st, const LinCfgReq *cfgreq) {
+    LinRun r;
+    r.ctx = ctx; r.dh = dh; r.opts = opts; r.keyed = keyed; r.out_dev = out_dev; r.sum = sum; r.st = st; r.cfgreq = cfgreq;
+    r.n = dh->n;
+    r.K = keyed ? dh->n_keys : 1;
+    if (r.K >= (1LL << 23)) throw_jh(JH_EUNSUPPORTED, "more than 2^23 keys in one call");
+    if (r.n >= (1LL << 31)) throw_jh(JH_EUNSUPPORTED, "more than 2^31 entries in one call");
+    r.budget = opts && opts->budget > 0 ? opts->budget : JH_DEFAULT_BUDGET;
+    r.init = opts ? opts->init_value : JH_NIL;
+    r.lflags = opts ? opts->flags : 0;
+    r.linear_mode = (opts && opts->algorithm == JH_ALGO_LINEAR) || cfgreq;
+    HIP_TRY(hipEventRecord(ctx->ev[EV_START], st));
+
+    r.prepare();
+    r.memo_generation();
+    r.phase1_tables();
+    r.phase1_args();
+    r.phase1_resume();
+    r.phase2_budgets();
+
+    if (r.stream_p2) {
+        r.run_streaming();
+    } else {
+        r.run_phase1();
+        if (r.p1_only) {
+            r.run_stage1();
+        } else {
+            r.launch_xw();
+            if (r.n_defer == 0) r.record_no_heavy_keys();
+            else if (r.use_wg) r.run_wg_mode();
+            else if (r.linear_mode) r.run_linear();
+            else r.run_race();
+        }
+        if (r.n_x > 0) HIP_TRY(hipStreamWaitEvent(st, ctx->ev[EV_XW_END], 0));
+    }
+    HIP_TRY(hipEventRecord(ctx->ev[EV_SEARCHED], st));
+    r.diag_defer_timeline();
+    ctx->gen_base += r.gen_span;
+
+    r.finish();
 }
 
 // The per-key row index (CSR) of an independent history: the same stable
@@ -8178,22 +8229,15 @@ void key_index(jh_ctx *ctx, const jh_history *dh, int64_t *key_off, int64_t *row
     const int64_t n = dh->n, K = dh->n_keys;
     if (K >= (1LL << 31) - 2) throw_jh(JH_EUNSUPPORTED, "more than 2^31 keys");
     if (n >= (1LL << 32) - 1) throw_jh(JH_EUNSUPPORTED, "more than 2^32 entries");
-    uint32_t *kA = ctx->ws<uint32_t>(WS_KEYS_A, n), *kB = ctx->ws<uint32_t>(WS_KEYS_B, n);
-    uint32_t *rA = ctx->ws<uint32_t>(WS_ROWS_A, n), *rB = ctx->ws<uint32_t>(WS_ROWS_B, n);
-    uint32_t *off = ctx->ws<uint32_t>(WS_SEG_OFF, K + 2);
+    KeyPartition kp = partition_buffers(ctx, n);
+    kp.off = ctx->ws<uint32_t>(WS_SEG_OFF, K + 2);
     RangeOut *ro = ctx->ws<RangeOut>(WS_MISC, 1);
     int64_t *wide = ctx->ws<int64_t>(WS_C_TMP, std::max<int64_t>(n, K + 1));
     if (n > 0) {
-        k_keys<<<grid_for(n, 256), 256, 0, st>>>(dh->key, n, K, 1, kA, rA);
-        const int endbit = bits_for((uint64_t)K);
-        size_t tb = 0;
-        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, kA, kB, rA, rB, (int)n, 0, endbit, st));
-        void *tmp = ctx->ws<char>(WS_SORT_TMP, tb);
-        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, tb, kA, kB, rA, rB, (int)n, 0, endbit, st));
-        k_seg_off<<<grid_for(K + 1, 256), 256, 0, st>>>(kB, n, K, off, ro);
-        k_widen<<<grid_for(n, 256), 256, 0, st>>>(rB, n, wide);
+        partition_by_key(ctx, kp, dh->key, n, K, true, ro, st);
+        k_widen<<<grid_for(n, 256), 256, 0, st>>>(kp.rB, n, wide);
         HIP_TRY(hipMemcpyAsync(rows, wide, sizeof(int64_t) * n, hipMemcpyDeviceToHost, st));
-        k_widen<<<grid_for(K + 1, 256), 256, 0, st>>>(off, K + 1, wide);
+        k_widen<<<grid_for(K + 1, 256), 256, 0, st>>>(kp.off, K + 1, wide);
         HIP_TRY(hipMemcpyAsync(key_off, wide, sizeof(int64_t) * (K + 1), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
     } else {
