@@ -27,6 +27,9 @@
  *                                                   jepsen/src/jepsen/tests/long_fork.clj:158-324
  *   jh_check_causal_reverse   <- (independent/checker (jepsen.tests.causal-reverse/checker))
  *                                                   jepsen/src/jepsen/tests/causal_reverse.clj:21-84
+ *   jh_check_cycle            <- (jepsen.tests.cycle/checker (cycle/combine ...))
+ *                                                   jepsen/src/jepsen/tests/cycle.clj:202-216,911-934
+ *   jh_scc                    <- cycle/tarjan       jepsen/src/jepsen/tests/cycle.clj:150-160
  *
  * Plain pointers and sizes only. The caller owns every buffer; the library
  * never retains a caller pointer after returning. All entry points are
@@ -82,6 +85,13 @@
  * value2 = their number (the set-read layout; a nil or empty :value has
  * value2 = 0, and then value is not looked at). `key` as in
  * jh_check_cas_independent; key == NULL or n_keys == 0 is one un-keyed history.
+ *
+ * Cycle txns (jh_check_cycle with JH_CY_WR only): an :ok txn row has value = the
+ * index of its first micro-op and value2 = its number of micro-ops; micro-op j
+ * is the triple aux[3*(value+j) .. +3) = [f, k, v] with f = JH_F_READ /
+ * JH_F_WRITE, k an int64 the caller interned and v an int64 or JH_NIL; n_aux is
+ * a multiple of 3. A nil :value is value = JH_NIL, value2 = 0. Rows of other
+ * types are not read.
  */
 #ifndef JH_H
 #define JH_H
@@ -829,6 +839,120 @@ typedef struct jh_causal_reverse_result {
 int jh_check_causal_reverse(jh_ctx *ctx, const jh_history *h, const jh_causal_reverse_opts *opts,
                             jh_causal_reverse_result *res, int32_t *key_valid, int64_t *errors_out, int64_t err_cap,
                             int64_t *missing_out, int64_t missing_cap, char *err, size_t errlen);
+
+/* (jepsen.tests.cycle/checker (cycle/combine ...)), tests/cycle.clj:202-216,
+ * 911-934, and cycle/tarjan, cycle.clj:150-160 (additive to ABI 8: new structs,
+ * one cause code and two symbols). Vertices are history rows (jh_scc: 0..n-1);
+ * only completion rows ever carry edges. Rows with process == -1 (:nemesis) are
+ * skipped by every builder: they are never an invoke, an :ok source or a txn,
+ * which gives what the reference's removing them first gives (cycle.clj:919)
+ * while the vertices stay history rows; other non-integer processes stay.
+ *
+ * Analyzers (opts->analyzers, a mask; at least one, or n_extra > 0):
+ *  JH_CY_PROCESS   process-graph, cycle.clj:271-300: over the :ok rows, each row
+ *                  links to the next :ok row of the same process.
+ *  JH_CY_REALTIME  realtime-graph, cycle.clj:315-377, in closed form. Every
+ *                  invoke is paired with the next completion of its process
+ *                  (knossos' pair-index). For an :ok completion at row c let
+ *                  R(c) be the smallest completion row over the ops invoked
+ *                  after c whose completion is :ok (none: the end of the
+ *                  history); the reference's `oks` buffer holds c exactly during
+ *                  (c, R(c)), so c links to the completion, of any type, of
+ *                  every invoke whose row lies in (c, R(c)).
+ *                  A double invoke, or an :ok / :fail with no open invoke (an
+ *                  :info without one is left unpaired, as pair-index leaves it)
+ *                  -> valid = JH_UNKNOWN, cause JH_CAUSE_DOUBLE_INVOKE /
+ *                  JH_CAUSE_ORPHAN, unknown_row = the smallest such row
+ *                  (pair-index is not vendored: parity-unpinned). An invoke
+ *                  without a completion that stands after the first :ok row ->
+ *                  JH_UNKNOWN / JH_CAUSE_UNMATCHED_INVOKE, unknown_row = the
+ *                  smallest such row (link's assert, cycle.clj:99-104, throws
+ *                  there and check-safe makes it :unknown).
+ *  JH_CY_WR        wr-graph, cycle.clj:703-779 with txn/src/jepsen/txn.clj:5-28,
+ *                  over the :ok rows of any process, txns encoded as below. The
+ *                  external read of k is the value of the txn's first micro-op
+ *                  on k when that is not a write; the external write of k is the
+ *                  value of its last write to k. For every externally read
+ *                  (k, v), nil being a value like any other: no :ok writer of
+ *                  k = v: no edge; one: an edge from the writer to every reader
+ *                  (a txn reading its own (k, v) gives a self-loop, kept in
+ *                  edges_out, and changing nothing); two or more: valid =
+ *                  JH_UNKNOWN, cause JH_CAUSE_MULTIPLE_WRITES, unknown_row = the
+ *                  smallest reader row with such a pair, unknown_key /
+ *                  unknown_value = that row's first such pair in micro-op order,
+ *                  unknown_rows = its two smallest writer rows. A (k, v) written
+ *                  twice and never read externally is not an error.
+ *  extra edges     opts->extra_src / extra_dst / n_extra: host int64 history rows
+ *                  (monotonic-key and append edges are built by the shim).
+ * With several unknown causes the first of: double invoke, orphan, unmatched
+ * invoke, multiple writes is reported; edges and SCCs are not computed then.
+ *
+ * Txn encoding (JH_CY_WR only): an :ok txn row has value = the index of its
+ * first micro-op and value2 = its number of micro-ops; micro-op j is the triple
+ * aux[3*(value+j) .. +3) = [f, k, v], f = JH_F_READ / JH_F_WRITE, k an int64 the
+ * caller interned, v an int64 or JH_NIL; n_aux is a multiple of 3. A nil :value
+ * is value = JH_NIL, value2 = 0. Rows of other types are not read.
+ *
+ * SCCs. An edge with dst < src is a back edge; every cycle holds one, and the
+ * row intervals [dst, src] of the back edges, merged where they overlap, are
+ * the regions: every SCC of more than one vertex lies inside one region. Each
+ * region of two or more vertices is searched by one workgroup (worklist
+ * trimming, then pivots with backward / forward reach), its per-vertex state in
+ * LDS when it has at most JH_CY_LDS_VERTICES vertices and in device memory
+ * otherwise. Work cap: a region of V vertices and E edges (both CSRs count E
+ * once) may visit at most JH_CY_WORK_MULT * (V + E) edges; past that the call
+ * returns JH_EUNSUPPORTED.
+ *
+ * Outputs (any may be NULL; every count is complete whatever the caps):
+ *  labels_out[n]  for each row the smallest row of its SCC, -1 when in none.
+ *  scc_off / scc_rows  the SCCs ordered by (size, smallest row): scc_off gets
+ *                 min(scc_count, scc_cap) + 1 offsets and scc_rows the member
+ *                 rows, ascending within an SCC, of those SCCs, as far as
+ *                 rows_cap reaches (offsets past rows_cap are still exact).
+ *  edges_out      min(total edges, edge_cap) [src_row, dst_row] pairs, order
+ *                 unspecified, repeats across analyzers allowed.
+ *
+ * JH_EUNSUPPORTED (the shim falls back): a micro-op f other than read / write; a
+ * txn of more than JH_CY_MAX_MOPS micro-ops; more than 2^31 - 2 vertices or
+ * edges; a region past the work cap. JH_EINVAL: a txn range leaving
+ * [0, n_aux / 3), a negative count, n_aux % 3 != 0, an edge endpoint outside
+ * [0, n), analyzers == 0 with no extra edges, a :type outside 0..3, path 1
+ * forced with a region of more than JH_CY_LDS_VERTICES vertices. */
+#define JH_CAUSE_UNMATCHED_INVOKE 12     /* cycle: an invoke without completion after the first :ok */
+#define JH_CY_PROCESS  1
+#define JH_CY_REALTIME 2
+#define JH_CY_WR       4
+#define JH_CY_LDS_VERTICES 2048          /* vertices of a region of the on-chip tier (16 B each) */
+#define JH_CY_MAX_MOPS 64                /* micro-ops per txn */
+#define JH_CY_WORK_MULT 64               /* work cap of a region: this * (vertices + edges) edge visits */
+
+typedef struct jh_cycle_opts {
+    int32_t analyzers;    /* mask of JH_CY_*; ignored by jh_scc */
+    int32_t path;         /* 0 auto, 1 on-chip tier, 2 global tier; tests force both */
+    const int64_t *extra_src, *extra_dst;   /* host pointers; ignored by jh_scc */
+    int64_t n_extra;
+    int64_t reserved[4];
+} jh_cycle_opts;
+
+typedef struct jh_cycle_result {
+    int32_t valid, cause;          /* JH_VALID iff scc_count == 0; JH_UNKNOWN with a cause above */
+    int32_t path;                  /* 1: every region on chip, 2: some region in the global tier, 0: no region */
+    int32_t pad;
+    int64_t scc_count, scc_vertices;
+    int64_t edge_count[4];         /* process, realtime, wr, extra (jh_scc: all in [3]); self-loops and repeats counted */
+    int64_t back_edges;
+    int64_t regions, max_region, global_regions;   /* regions of >= 2 vertices; the largest one's vertices */
+    int64_t unknown_row, unknown_key, unknown_value, unknown_rows[2];   /* -1 / JH_NIL / JH_NIL / -1 when unused */
+    int64_t entries;               /* micro-ops scanned */
+    double device_ms;
+} jh_cycle_result;
+
+int jh_scc(jh_ctx *ctx, int64_t n_vertices, const int64_t *src, const int64_t *dst, int64_t n_edges,
+           const jh_cycle_opts *opts, jh_cycle_result *res, int64_t *labels_out, int64_t *scc_off, int64_t *scc_rows,
+           int64_t scc_cap, int64_t rows_cap, char *err, size_t errlen);
+int jh_check_cycle(jh_ctx *ctx, const jh_history *h, const jh_cycle_opts *opts, jh_cycle_result *res,
+                   int64_t *labels_out, int64_t *scc_off, int64_t *scc_rows, int64_t scc_cap, int64_t rows_cap,
+                   int64_t *edges_out, int64_t edge_cap, char *err, size_t errlen);
 
 #ifdef __cplusplus
 }

@@ -254,6 +254,30 @@ class JhCausalReverseResult(C.Structure):
                 ("device_ms", C.c_double)]
 
 
+CY_PROCESS, CY_REALTIME, CY_WR = 1, 2, 4
+CY_PATH_AUTO, CY_PATH_LDS, CY_PATH_GLOBAL = 0, 1, 2
+CY_LDS_VERTICES = 2048        # JH_CY_LDS_VERTICES: vertices of a region of the on-chip tier
+CY_MAX_MOPS = 64              # JH_CY_MAX_MOPS: micro-ops per txn
+CY_WORK_MULT = 64             # JH_CY_WORK_MULT: a region's work cap is this * (vertices + edges)
+CY_SCC_CAP = 8                # cycle.clj:926: (take 8) of the sorted SCCs
+CAUSE_DOUBLE_INVOKE, CAUSE_ORPHAN, CAUSE_UNMATCHED_INVOKE = 3, 4, 12
+CAUSES[12] = "unmatched-invoke"
+
+
+class JhCycleOpts(C.Structure):
+    _fields_ = [("analyzers", C.c_int32), ("path", C.c_int32), ("extra_src", _p64), ("extra_dst", _p64),
+                ("n_extra", C.c_int64), ("reserved", C.c_int64 * 4)]
+
+
+class JhCycleResult(C.Structure):
+    _fields_ = [("valid", C.c_int32), ("cause", C.c_int32), ("path", C.c_int32), ("pad", C.c_int32),
+                ("scc_count", C.c_int64), ("scc_vertices", C.c_int64), ("edge_count", C.c_int64 * 4),
+                ("back_edges", C.c_int64), ("regions", C.c_int64), ("max_region", C.c_int64),
+                ("global_regions", C.c_int64), ("unknown_row", C.c_int64), ("unknown_key", C.c_int64),
+                ("unknown_value", C.c_int64), ("unknown_rows", C.c_int64 * 2), ("entries", C.c_int64),
+                ("device_ms", C.c_double)]
+
+
 # numpy structured dtype with the same layout as jh_key_verdict
 try:
     import numpy as _np

@@ -78,6 +78,10 @@ def lib():
             L.jh_check_causal_reverse.argtypes = [C.c_void_p, H, C.POINTER(A.JhCausalReverseOpts),
                                                   C.POINTER(A.JhCausalReverseResult), C.POINTER(C.c_int32), p64,
                                                   C.c_int64, p64, C.c_int64, C.c_char_p, C.c_size_t]
+            L.jh_scc.argtypes = [C.c_void_p, C.c_int64, p64, p64, C.c_int64, C.POINTER(A.JhCycleOpts),
+                                 C.POINTER(A.JhCycleResult), p64, p64, p64, C.c_int64, C.c_int64, C.c_char_p, C.c_size_t]
+            L.jh_check_cycle.argtypes = [C.c_void_p, H, C.POINTER(A.JhCycleOpts), C.POINTER(A.JhCycleResult), p64, p64,
+                                         p64, C.c_int64, C.c_int64, p64, C.c_int64, C.c_char_p, C.c_size_t]
             L.jh_host_alloc.argtypes = [C.c_size_t, C.POINTER(C.c_void_p), C.c_char_p, C.c_size_t]
             L.jh_host_free.argtypes = [C.c_void_p]
             # history ingest (include/jh_io.h), host code in the same library
@@ -112,6 +116,7 @@ EXPORTED_SYMBOLS = ["jh_version", "jh_open", "jh_open_multi", "jh_open_devices",
                     "jh_check_cas", "jh_check_cas_independent_device", "jh_lin_configs", "jh_check_counter",
                     "jh_check_set", "jh_check_set_bitmaps", "jh_check_set_full", "jh_check_set_full_opts", "jh_check_total_queue", "jh_check_queue",
                     "jh_check_unique_ids", "jh_check_bank", "jh_check_long_fork", "jh_check_causal_reverse",
+                    "jh_scc", "jh_check_cycle",
                     "jh_host_alloc", "jh_host_free",
                     # include/jh_io.h
                     "jh_ingest_file", "jh_ingest_buffer", "jh_ingest_file_opts", "jh_ingest_buffer_opts", "jh_ingest_history", "jh_ingest_time",
@@ -525,6 +530,59 @@ class Context:
         out["key_valid"] = kv
         out["errors"] = (errs[:5 * min(r.error_count, ecap)] if ecap else np.zeros(0, np.int64)).reshape(-1, 5)
         out["missing"] = miss[:min(r.missing_total, mcap)] if mcap else np.zeros(0, np.int64)
+        return out
+
+    # -- cycle ----------------------------------------------------------------
+    @staticmethod
+    def _cycle_out(r, labels, off, rows, scc_cap):
+        out = {name: getattr(r, name) for name, _ in A.JhCycleResult._fields_ if name != "pad"}
+        out["edge_count"] = list(r.edge_count)
+        out["unknown_rows"] = list(r.unknown_rows)
+        out["labels"] = labels
+        k = min(r.scc_count, scc_cap)
+        out["sccs"] = [rows[off[i]:off[i + 1]].tolist() for i in range(k) if off[i + 1] <= len(rows)]
+        return out
+
+    def scc(self, n, src, dst, path=0, scc_cap=A.CY_SCC_CAP, rows_cap=None, want_labels=True):
+        """jh_scc: the result fields plus `labels` (per vertex the smallest
+        vertex of its SCC, or -1; None unless want_labels) and `sccs`, the
+        member lists of the first scc_cap SCCs by (size, smallest vertex) that
+        fit rows_cap (default n; 0 without labels)."""
+        src, dst = np.ascontiguousarray(src, np.int64), np.ascontiguousarray(dst, np.int64)
+        n = int(n)
+        scc_cap = max(int(scc_cap), 0)
+        rows_cap = (n if want_labels else 0) if rows_cap is None else max(int(rows_cap), 0)
+        labels = np.full(max(n, 1), -1, np.int64) if want_labels else None
+        off, rows = np.zeros(scc_cap + 1, np.int64), np.zeros(max(rows_cap, 1), np.int64)
+        r, o = A.JhCycleResult(), A.JhCycleOpts(path=int(path))
+        err = C.create_string_buffer(1024)
+        rc = lib().jh_scc(self._h, n, A.ptr64(src), A.ptr64(dst), len(src), C.byref(o), C.byref(r), A.ptr64(labels),
+                          A.ptr64(off), A.ptr64(rows), scc_cap, rows_cap, err, len(err))
+        _raise(rc, err)
+        return self._cycle_out(r, labels[:n] if want_labels else None, off, rows[:rows_cap], scc_cap)
+
+    def check_cycle(self, cols, analyzers, path=0, extra=None, scc_cap=A.CY_SCC_CAP, rows_cap=None, edge_cap=0,
+                    on_device=False):
+        """jh_check_cycle: the result fields plus `labels`, `sccs` (as `scc`)
+        and `edges`, a (k, 2) array of [src_row, dst_row], k = min(edges,
+        edge_cap). extra: (src, dst) rows of edges built by the caller."""
+        h = A.make_history(cols, on_device=on_device)
+        n = int(cols.n)
+        scc_cap = max(int(scc_cap), 0)
+        rows_cap = n if rows_cap is None else max(int(rows_cap), 0)
+        ecap = max(int(edge_cap), 0)
+        labels, off, rows = np.full(max(n, 1), -1, np.int64), np.zeros(scc_cap + 1, np.int64), np.zeros(max(rows_cap, 1), np.int64)
+        edges = np.zeros(2 * max(ecap, 1), np.int64)
+        r, o = A.JhCycleResult(), A.JhCycleOpts(analyzers=int(analyzers), path=int(path))
+        if extra is not None:
+            xs, xd = np.ascontiguousarray(extra[0], np.int64), np.ascontiguousarray(extra[1], np.int64)
+            o.extra_src, o.extra_dst, o.n_extra = A.ptr64(xs), A.ptr64(xd), len(xs)
+        err = C.create_string_buffer(1024)
+        rc = lib().jh_check_cycle(self._h, C.byref(h), C.byref(o), C.byref(r), A.ptr64(labels), A.ptr64(off),
+                                  A.ptr64(rows), scc_cap, rows_cap, A.ptr64(edges) if ecap else None, ecap, err, len(err))
+        _raise(rc, err)
+        out = self._cycle_out(r, labels[:n], off, rows[:rows_cap], scc_cap)
+        out["edges"] = edges[:2 * min(sum(r.edge_count), ecap)].reshape(-1, 2)
         return out
 
 

@@ -686,3 +686,5 @@ from . import bank  # noqa: E402,F401
 from . import long_fork  # noqa: E402,F401
 # and jepsen.tests.causal-reverse (tests/causal_reverse.clj): checker.causal_reverse.checker()
 from . import causal_reverse  # noqa: E402,F401
+# and jepsen.tests.cycle (tests/cycle.clj): checker.cycle.checker(analyze_fn)
+from . import cycle  # noqa: E402,F401

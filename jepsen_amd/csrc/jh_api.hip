@@ -563,4 +563,47 @@ int jh_check_causal_reverse(jh_ctx *ctx, const jh_history *h, const jh_causal_re
     });
 }
 
+int jh_scc(jh_ctx *ctx, int64_t n_vertices, const int64_t *src, const int64_t *dst, int64_t n_edges,
+           const jh_cycle_opts *opts, jh_cycle_result *res, int64_t *labels_out, int64_t *scc_off, int64_t *scc_rows,
+           int64_t scc_cap, int64_t rows_cap, char *err, size_t errlen) {
+    if (!ctx || !res || !opts) { set_err(err, errlen, "null argument"); return JH_EINVAL; }
+    if (opts->path < 0 || opts->path > 2) { set_err(err, errlen, "path is 0, 1 or 2"); return JH_EINVAL; }
+    if (n_vertices < 0 || n_edges < 0) { set_err(err, errlen, "scc: a negative count"); return JH_EINVAL; }
+    ctx = primary(ctx);
+    std::lock_guard<std::mutex> g(ctx->mu);
+    return guarded(err, errlen, [&] {
+        HIP_TRY(hipSetDevice(ctx->device));
+        const CycleOut out = {labels_out, scc_off, scc_rows, scc_cap, rows_cap, nullptr, 0};
+        scc_check(ctx, n_vertices, src, dst, n_edges, opts, res, out, ctx->stream);
+    });
+}
+
+int jh_check_cycle(jh_ctx *ctx, const jh_history *h, const jh_cycle_opts *opts, jh_cycle_result *res,
+                   int64_t *labels_out, int64_t *scc_off, int64_t *scc_rows, int64_t scc_cap, int64_t rows_cap,
+                   int64_t *edges_out, int64_t edge_cap, char *err, size_t errlen) {
+    if (!ctx || !res || !opts) { set_err(err, errlen, "null argument"); return JH_EINVAL; }
+    if (opts->path < 0 || opts->path > 2) { set_err(err, errlen, "path is 0, 1 or 2"); return JH_EINVAL; }
+    if (opts->n_extra < 0) { set_err(err, errlen, "cycle: n_extra < 0"); return JH_EINVAL; }
+    if ((opts->analyzers & ~(JH_CY_PROCESS | JH_CY_REALTIME | JH_CY_WR)) != 0) {
+        set_err(err, errlen, "cycle: an unknown analyzer bit");
+        return JH_EINVAL;
+    }
+    if (opts->analyzers == 0 && opts->n_extra == 0) {
+        set_err(err, errlen, "cycle: no analyzer and no extra edges");
+        return JH_EINVAL;
+    }
+    ctx = primary(ctx);
+    std::lock_guard<std::mutex> g(ctx->mu);
+    return guarded(err, errlen, [&] {
+        check_hist(h);
+        const bool wr = (opts->analyzers & JH_CY_WR) != 0;
+        if (wr && (h->n_aux < 0 || h->n_aux % 3 != 0)) throw_jh(JH_EINVAL, "cycle: n_aux must be a multiple of 3 and >= 0");
+        if (wr && h->n_aux > 0 && !h->aux) throw_jh(JH_EINVAL, "cycle: n_aux > 0 without aux");
+        HIP_TRY(hipSetDevice(ctx->device));
+        jh_history d = stage_history(ctx, h, false, wr);
+        const CycleOut out = {labels_out, scc_off, scc_rows, scc_cap, rows_cap, edges_out, edge_cap};
+        cycle_check(ctx, &d, opts, res, out, ctx->stream);
+    });
+}
+
 }  // extern "C"

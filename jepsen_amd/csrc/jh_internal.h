@@ -130,6 +130,9 @@ enum WsSlot {
     WS_LF_FLAG, WS_LF_SKEY, WS_LF_SMASK, WS_LF_SROW, WS_LF_PC, WS_LF_OUT,
     WS_CR_META, WS_CR_WORDS, WS_CR_TCNT, WS_CR_TBASE, WS_CR_TMP, WS_CR_WKEY, WS_CR_WVAL, WS_CR_RKEY, WS_CR_RPERM, WS_CR_RROW,
     WS_CR_OFF, WS_CR_TIER, WS_CR_KV, WS_CR_EXP, WS_CR_MISS, WS_CR_SOFF, WS_CR_SCRATCH, WS_CR_OUT, WS_CR_SEG, WS_CR_MBUF,
+    WS_CY_META, WS_CY_TMP, WS_CY_PKEY, WS_CY_PROW, WS_CY_COMP, WS_CY_REV, WS_CY_IP, WS_CY_ICOMP, WS_CY_CNT,
+    WS_CY_TXN, WS_CY_REC, WS_CY_HASH, WS_CY_HIDX, WS_CY_RAW, WS_CY_EDGES, WS_CY_REACH, WS_CY_BS, WS_CY_REG, WS_CY_SEL,
+    WS_CY_FWD, WS_CY_BWD, WS_CY_CSR, WS_CY_STATE, WS_CY_LABEL, WS_CY_SIZE, WS_CY_KEYS, WS_CY_VALS,
     WS_COUNT
 };
 
@@ -215,3 +218,11 @@ void long_fork_check(jh_ctx *ctx, const jh_history *dh, const jh_long_fork_opts 
 void causal_reverse_check(jh_ctx *ctx, const jh_history *dh, const jh_causal_reverse_opts *opts,
                           jh_causal_reverse_result *res, int32_t *key_valid, int64_t *errors_out, int64_t err_cap,
                           int64_t *missing_out, int64_t missing_cap, hipStream_t stream);
+// cycle (jh_cycle.hip); src / dst are host edge lists, the outputs host buffers (any may be null)
+struct CycleOut {
+    int64_t *labels, *scc_off, *scc_rows, scc_cap, rows_cap, *edges, edge_cap;
+};
+void scc_check(jh_ctx *ctx, int64_t n, const int64_t *src, const int64_t *dst, int64_t n_edges,
+               const jh_cycle_opts *opts, jh_cycle_result *res, const CycleOut &out, hipStream_t stream);
+void cycle_check(jh_ctx *ctx, const jh_history *dh, const jh_cycle_opts *opts, jh_cycle_result *res,
+                 const CycleOut &out, hipStream_t stream);

@@ -1,0 +1,585 @@
+"""jepsen.tests.cycle on MI355X: dependency graphs over completion ops, their
+strongly connected components, and an explanation of each.
+
+Mirrors jepsen/src/jepsen/tests/cycle.clj (names, argument meaning, result
+maps). An analyzer is a function history -> (Graph, explainer); `combine` takes
+the union; `checker(analyze_fn)` removes the :nemesis ops, analyzes, and reports
+every SCC of more than one op as an anomaly:
+
+    {"valid?": bool, "scc-count": int, "cycles": [[op, why, op, ..., op], ...]}
+
+Vertices are positions in the history the analyzer was given (the checker gives
+every op an "index" first, so they are history rows). The module's own analyzers
+(process_graph, realtime_graph, wr_graph and their `combine`) carry a mask of
+JH_CY_* bits: a checker over them makes ONE jh_check_cycle call when the values
+encode (include/jh.h, "Cycle txns": keys are interned, values must be longs or
+nil) and runs the host implementation otherwise. The host implementation is the
+numpy closed forms below; tests/cycle_ref.py holds the literal transcriptions
+they are tested against. Explanations run on the host over the at most 8
+reported SCCs.
+
+Deviations: SCCs of equal size are ordered by their smallest
+row (Bifurcan's order is unpinned); find_cycle starts at the SCC's smallest row
+and follows successors in ascending row order (Bifurcan's first vertex is
+unpinned); a Python str key or value prints as a keyword.
+"""
+import numpy as np
+
+from . import _abi as A
+from . import history as H
+
+I64_MIN, I64_MAX = -(1 << 63), (1 << 63) - 1
+READ_FS, WRITE_FS = ("r", "read"), ("w", "write")
+
+
+class IllegalArgument(ValueError):
+    """IllegalArgumentException: wr-graph's value written by more than one op."""
+
+
+class IllegalHistory(AssertionError):
+    """An assert of knossos' pair-index or of cycle/link failed."""
+
+    def __init__(self, cause, row):
+        super().__init__(f"{cause} at index {row}")
+        self.cause, self.row = cause, row
+
+
+# -- graphs -----------------------------------------------------------------------
+class Graph:
+    """A directed graph over 0..n-1 as an (E, 2) int64 edge array."""
+
+    def __init__(self, n, edges=None):
+        self.n = int(n)
+        self.edges = np.zeros((0, 2), np.int64) if edges is None or len(edges) == 0 else \
+            np.asarray(edges, np.int64).reshape(-1, 2)
+
+    def out(self, v, within=None):
+        e = self.edges
+        succ = sorted(set(e[e[:, 0] == v, 1].tolist()))
+        return [s for s in succ if within is None or s in within]
+
+    def to_map(self):
+        """{vertex: sorted successors} over every vertex that carries an edge."""
+        m = {}
+        for s, d in self.edges.tolist():
+            m.setdefault(s, set()).add(d)
+            m.setdefault(d, set())
+        return {k: sorted(v) for k, v in sorted(m.items())}
+
+    def union(self, other):
+        return Graph(max(self.n, other.n), np.concatenate([self.edges, other.edges]))
+
+
+def map_to_graph(m):
+    """{node: successors} (cycle/map->bdigraph) -> Graph over 0..max node."""
+    edges = [(int(a), int(b)) for a, succ in m.items() for b in succ]
+    n = 1 + max([int(a) for a in m] + [b for _, b in edges], default=-1)
+    return Graph(n, edges)
+
+
+def _encode_rows(history):
+    proc = np.empty(len(history), np.int64)
+    typ = np.empty(len(history), np.int64)
+    others = {"nemesis": -1}
+    for i, op in enumerate(history):
+        p = op.get("process")
+        if H._is_int(p) and p >= 0:
+            proc[i] = int(p)
+        else:
+            proc[i] = others.setdefault(p, -1 - len(others)) if p != "nemesis" else -1
+        typ[i] = H.TYPES[op.get("type")]
+    return proc, typ
+
+
+# -- numpy closed forms -----------------------------------------------------------
+def process_edges(proc, typ):
+    """cycle.clj:271-300: each :ok row -> the next :ok row of its process."""
+    ok = np.nonzero((typ == A.TYPE_OK) & (proc != -1))[0]
+    o = ok[np.argsort(proc[ok], kind="stable")]
+    same = proc[o[:-1]] == proc[o[1:]] if len(o) > 1 else np.zeros(0, bool)
+    return np.stack([o[:-1][same], o[1:][same]], axis=1) if len(o) > 1 else np.zeros((0, 2), np.int64)
+
+
+def pair_rows(proc, typ):
+    """knossos' pair-index over the non-nemesis rows: comp[i] = the completion
+    row of the invoke at i (-1: none). IllegalHistory for a double invoke or an
+    :ok / :fail without an open invoke (an :info without one stays unpaired)."""
+    n = len(proc)
+    comp = np.full(n, -1, np.int64)
+    rows = np.nonzero(proc != -1)[0]
+    o = rows[np.argsort(proc[rows], kind="stable")]
+    if len(o) == 0:
+        return comp
+    t, p = typ[o], proc[o]
+    prev_inv = np.concatenate(([False], (p[1:] == p[:-1]) & (t[:-1] == A.TYPE_INVOKE)))
+    dbl = o[(t == A.TYPE_INVOKE) & prev_inv]
+    orphan = o[((t == A.TYPE_OK) | (t == A.TYPE_FAIL)) & ~prev_inv]
+    if len(dbl):
+        raise IllegalHistory("double-invoke", int(dbl.min()))
+    if len(orphan):
+        raise IllegalHistory("orphan-completion", int(orphan.min()))
+    done = np.concatenate(((p[1:] == p[:-1]) & (t[:-1] == A.TYPE_INVOKE) & (t[1:] != A.TYPE_INVOKE), [False]))
+    comp[o[done]] = o[np.nonzero(done)[0] + 1]
+    return comp
+
+
+def realtime_edges(proc, typ):
+    """cycle.clj:315-377 in closed form: an :ok completion c links to the
+    completion of every invoke in (c, R(c)), R(c) = the smallest completion row
+    over the ops invoked after c that complete :ok (none: the end)."""
+    n = len(proc)
+    comp = pair_rows(proc, typ)
+    inv = (typ == A.TYPE_INVOKE) & (proc != -1)
+    oks = np.nonzero((typ == A.TYPE_OK) & (proc != -1))[0]
+    if len(oks):
+        bad = np.nonzero(inv & (comp < 0) & (np.arange(n) > oks[0]))[0]
+        if len(bad):
+            raise IllegalHistory("unmatched-invoke", int(bad[0]))
+    key = np.full(n + 1, n, np.int64)
+    has_ok = inv & (comp >= 0)
+    has_ok[has_ok] = typ[comp[has_ok]] == A.TYPE_OK
+    key[:n][has_ok] = comp[has_ok]
+    suf = np.minimum.accumulate(key[::-1])[::-1]          # suf[i] = min key[i:]
+    r = suf[oks + 1]
+    ip = np.concatenate(([0], np.cumsum(inv)))             # invokes in rows < i
+    cnt = ip[r] - ip[oks + 1]
+    inv_comp = comp[inv]
+    src = np.repeat(oks, cnt)
+    first = np.repeat(ip[oks + 1], cnt)
+    within = np.arange(int(cnt.sum())) - np.repeat(np.cumsum(cnt) - cnt, cnt)
+    return np.stack([src, inv_comp[first + within]], axis=1) if len(src) else np.zeros((0, 2), np.int64)
+
+
+def ext_reads(txn):
+    """txn.clj:5-17: {k: v} of the values a txn observed and did not write."""
+    ext, ignore = {}, set()
+    for f, k, v in (txn or ()):
+        if f not in WRITE_FS and k not in ignore:
+            ext[k] = v
+        ignore.add(k)
+    return ext
+
+
+def ext_writes(txn):
+    """txn.clj:19-28: {k: v} of the final values a txn wrote."""
+    ext = {}
+    for f, k, v in (txn or ()):
+        if f not in READ_FS:
+            ext.pop(k, None)
+            ext[k] = v
+    return ext
+
+
+def ext_index(ext_fn, history):
+    """cycle.clj:703-719: {k: {v: [op, ...]}} over the :ok ops (each list newest
+    first, as conj on a list builds it)."""
+    idx = {}
+    for op in history:
+        if op.get("type") == "ok":
+            for k, v in ext_fn(op.get("value")).items():
+                idx.setdefault(k, {}).setdefault(v, []).insert(0, op)
+    return idx
+
+
+def wr_edges(history):
+    """cycle.clj:736-779 over positions: writer -> every external reader of its
+    (k, v). IllegalArgument when a read pair has two or more writers: the
+    smallest reader row, its first such pair in micro-op order."""
+    writers = {}
+    for i, op in enumerate(history):
+        if op.get("type") == "ok" and op.get("process") != "nemesis":
+            for k, v in ext_writes(op.get("value")).items():
+                writers.setdefault((k, v), []).append(i)
+    edges = []
+    for i, op in enumerate(history):
+        if op.get("type") == "ok" and op.get("process") != "nemesis":
+            for k, v in ext_reads(op.get("value")).items():
+                w = writers.get((k, v), ())
+                if len(w) > 1:
+                    e = IllegalArgument(f"Key {pr_str(k)} had value {pr_str(v)} written by more than one op: "
+                                        f"{[history[j] for j in w]!r}")
+                    e.row, e.key, e.value, e.rows = i, k, v, w[:2]
+                    raise e
+                if w:
+                    edges.append((w[0], i))
+    return np.asarray(edges, np.int64).reshape(-1, 2)
+
+
+def regions(n, edges):
+    """The merged row intervals [dst, src] of the back edges (dst < src) as an
+    (R, 2) array of [start, end], regions of two or more vertices only. Every
+    SCC of more than one vertex lies inside one of them."""
+    edges = np.asarray(edges, np.int64).reshape(-1, 2)
+    reach = np.arange(n, dtype=np.int64)
+    back = edges[edges[:, 1] < edges[:, 0]]
+    np.maximum.at(reach, back[:, 1], back[:, 0])
+    mx = np.maximum.accumulate(reach) if n else reach
+    start = np.ones(n, bool)
+    start[1:] = mx[:-1] < np.arange(1, n)
+    big = start & (reach > np.arange(n))
+    s = np.nonzero(big)[0]
+    e = np.nonzero((mx == np.arange(n)) & ~start)[0]
+    return np.stack([s, e], axis=1) if len(s) else np.zeros((0, 2), np.int64)
+
+
+def _tarjan_labels(n, edges, labels, base=0):
+    """Iterative Tarjan over vertices base..base+n-1: labels[v] = the smallest
+    vertex of v's SCC for the SCCs of more than one vertex."""
+    succ = [[] for _ in range(n)]
+    for s, d in edges:
+        succ[s - base].append(d - base)
+    index, low, on, stack, k = [-1] * n, [0] * n, [False] * n, [], 0
+    for root in range(n):
+        if index[root] >= 0:
+            continue
+        work = [(root, 0)]
+        while work:
+            v, i = work.pop()
+            if i == 0:
+                index[v] = low[v] = k
+                k += 1
+                stack.append(v)
+                on[v] = True
+            recurse = False
+            while i < len(succ[v]):
+                w = succ[v][i]
+                i += 1
+                if index[w] < 0:
+                    work.append((v, i))
+                    work.append((w, 0))
+                    recurse = True
+                    break
+                if on[w]:
+                    low[v] = min(low[v], index[w])
+            if recurse:
+                continue
+            if low[v] == index[v]:
+                comp = []
+                while True:
+                    w = stack.pop()
+                    on[w] = False
+                    comp.append(w)
+                    if w == v:
+                        break
+                if len(comp) > 1:
+                    for w in comp:
+                        labels[base + w] = base + min(comp)
+            if work:
+                u = work[-1][0]
+                low[u] = min(low[u], low[v])
+
+
+def scc_labels(n, edges):
+    """labels[v] = the smallest vertex of v's SCC, -1 when v is in none: Tarjan
+    inside each region of the back-edge decomposition (what the device does with
+    one workgroup per region)."""
+    edges = np.asarray(edges, np.int64).reshape(-1, 2)
+    labels = np.full(n, -1, np.int64)
+    reg = regions(n, edges)
+    if len(reg) == 0:
+        return labels
+    rid = np.searchsorted(reg[:, 0], edges, side="right") - 1
+    inside = (rid[:, 0] == rid[:, 1]) & (rid[:, 0] >= 0) & (edges[:, 0] != edges[:, 1])
+    inside[inside] = (edges[inside] <= reg[rid[inside, 0], 1][:, None]).all(axis=1)
+    for r in np.unique(rid[inside, 0]):
+        a, b = reg[r]
+        _tarjan_labels(int(b - a + 1), edges[inside & (rid[:, 0] == r)].tolist(), labels, int(a))
+    return labels
+
+
+def sccs_of(labels):
+    """The SCCs as ascending member lists, ordered by (size, smallest row)."""
+    groups = {}
+    for v in np.nonzero(labels >= 0)[0].tolist():
+        groups.setdefault(int(labels[v]), []).append(v)
+    return sorted(groups.values(), key=lambda g: (len(g), g[0]))
+
+
+def tarjan(graph):
+    """cycle.clj:155-160: the SCCs of more than one node of {node: successors}
+    (non-negative ints), as a list of sets."""
+    g = graph if isinstance(graph, Graph) else map_to_graph(graph)
+    return [set(c) for c in sccs_of(scc_labels(g.n, g.edges))]
+
+
+strongly_connected_components = tarjan
+
+
+# -- explainers ---------------------------------------------------------------------
+def pr_str(x):
+    if x is None:
+        return "nil"
+    if isinstance(x, bool):
+        return "true" if x else "false"
+    if isinstance(x, str):
+        return ":" + x
+    return repr(x)
+
+
+class ProcessExplainer:
+    def explain_pair(self, a, b):
+        if a.get("process") == b.get("process") and a["index"] < b["index"]:
+            return f"which process {a.get('process')} completed before"
+        return None
+
+
+class RealtimeExplainer:
+    """pairs: the invocation of a completion, found by walking back to the
+    latest invoke of its process."""
+
+    def __init__(self, history):
+        self.history = history
+        self.pos = {op["index"]: i for i, op in enumerate(history)}
+
+    def invocation(self, op):
+        for i in range(self.pos[op["index"]] - 1, -1, -1):
+            o = self.history[i]
+            if o.get("process") == op.get("process"):
+                return o if o.get("type") == "invoke" else None
+        return None
+
+    def explain_pair(self, a, b):
+        inv = self.invocation(b)
+        if inv is None or not a["index"] < inv["index"]:
+            return None
+        gap = ""
+        if a.get("time") is not None and inv.get("time") is not None:     # 0 is truthy in Clojure
+            gap = "%.3f seconds " % ((inv["time"] - a["time"]) / 1e9)
+        return "which completed" + gap + " before the invocation of"
+
+
+class WRExplainer:
+    def explain_pair(self, a, b):
+        writes, reads = ext_writes(a.get("value")), ext_reads(b.get("value"))
+        for k in reads:
+            if reads.get(k) == writes.get(k):
+                return f"which wrote {pr_str(k)} = {pr_str(writes.get(k))}, which was read by"
+        return None
+
+
+class CombinedExplainer:
+    def __init__(self, explainers):
+        self.explainers = list(explainers)
+
+    def explain_pair(self, a, b):
+        for e in self.explainers:
+            s = e.explain_pair(a, b)
+            if s is not None:
+                return s
+        return None
+
+
+# -- analyzers ----------------------------------------------------------------------
+def _indexed(history):
+    return [op if "index" in op else dict(op, index=i) for i, op in enumerate(history)]
+
+
+def process_graph(history):
+    history = list(history)
+    proc, typ = _encode_rows(history)
+    return Graph(len(history), process_edges(proc, typ)), ProcessExplainer()
+
+
+def realtime_graph(history):
+    history = _indexed(history)
+    proc, typ = _encode_rows(history)
+    return Graph(len(history), realtime_edges(proc, typ)), RealtimeExplainer(history)
+
+
+def wr_graph(history):
+    history = list(history)
+    return Graph(len(history), wr_edges(history)), WRExplainer()
+
+
+process_graph.analyzers, realtime_graph.analyzers, wr_graph.analyzers = A.CY_PROCESS, A.CY_REALTIME, A.CY_WR
+
+
+def combine(*analyzers):
+    """cycle.clj:202-216: the union of the analyzers' graphs."""
+    def analyze(history):
+        history = list(history)
+        g, ex = Graph(len(history)), []
+        for an in analyzers:
+            g2, e = an(history)
+            g, ex = g.union(g2), ex + [e]
+        return g, CombinedExplainer(ex)
+    masks = [getattr(an, "analyzers", None) for an in analyzers]
+    analyze.analyzers = None if None in masks or not masks else int(np.bitwise_or.reduce(masks))
+    analyze.parts = analyzers
+    return analyze
+
+
+# -- cycles -------------------------------------------------------------------------
+def prune_alternate_paths(paths):
+    first = {}
+    for p in paths:
+        first.setdefault(p[-1], p)
+    return list(first.values())
+
+
+def prune_longer_paths(paths):
+    old = {v for p in paths for v in p[:-1]}
+    return [p for p in paths if p[-1] not in old]
+
+
+def grow_paths(g, paths, within=None):
+    return [p + [s] for p in paths for s in g.out(p[-1], within)]
+
+
+def path_shells(g, start, within=None):
+    """cycle.clj:825-832: longer and longer paths from start (a generator)."""
+    paths = [[start]]
+    while True:
+        yield paths
+        paths = prune_alternate_paths(grow_paths(g, prune_longer_paths(paths), within))
+
+
+def find_cycle(graph, scc):
+    """cycle.clj:868-882: a short cycle in the SCC, from its smallest vertex."""
+    within = set(scc)
+    for k, shell in enumerate(path_shells(graph, min(within), within)):
+        for p in shell:
+            if len(p) > 1 and p[0] == p[-1]:
+                return p
+        if k > len(within) + 1 or not shell:
+            raise RuntimeError(f"no cycle through {min(within)} in {sorted(within)}")
+
+
+def explain_scc(graph, explainer, scc, history):
+    """cycle.clj:884-909: [op why op why ... op] around a cycle of the SCC."""
+    cyc = find_cycle(graph, scc)
+    out = [history[cyc[0]]]
+    for a, b in zip(cyc, cyc[1:]):
+        why = explainer.explain_pair(history[a], history[b])
+        if why is None:
+            raise RuntimeError(f"Explainer {explainer!r} was unable to explain the relationship between "
+                               f"{history[a]!r} and {history[b]!r}")
+        out += [why, history[b]]
+    return out
+
+
+# -- encoding -----------------------------------------------------------------------
+def _long(x):
+    if x is None:
+        return A.NIL
+    if not H._is_int(x) or not I64_MIN < x <= I64_MAX:
+        raise TypeError(f"cycle: value {x!r} has no encoding")
+    return int(x)
+
+
+def encode(history, txns=True):
+    """Op maps -> Columns (include/jh.h, "Cycle txns"). txns: encode the :ok
+    rows' :value as micro-op triples (keys interned in first-appearance order;
+    TypeError for a value that is no long, a micro-op that is no read / write or
+    a :value that is no sequence of triples)."""
+    history = list(history)
+    n = len(history)
+    proc, typ = _encode_rows(history)
+    val, val2 = np.full(n, A.NIL, np.int64), np.zeros(n, np.int64)
+    aux, key_ids = [], {}
+    if txns:
+        for i, op in enumerate(history):
+            v = op.get("value")
+            if op.get("type") != "ok" or op.get("process") == "nemesis" or v is None:
+                continue
+            if not isinstance(v, (list, tuple)):
+                raise TypeError(f"cycle: a txn of {v!r}")
+            val[i], val2[i] = len(aux) // 3, len(v)
+            for mop in v:
+                f, k, x = mop
+                if f not in READ_FS + WRITE_FS:
+                    raise TypeError(f"cycle: a micro-op {f!r}")
+                aux += [A.F_READ if f in READ_FS else A.F_WRITE, key_ids.setdefault(k, len(key_ids)), _long(x)]
+    return H.Columns(n=n, process=proc, type=typ, f=np.full(n, A.F_FIRST_INTERNED, np.int64), key=None, value=val,
+                     value2=val2, n_keys=0, aux=np.asarray(aux if aux else [0, 0, 0], np.int64)[:max(len(aux), 3)],
+                     keys=list(key_ids))
+
+
+# -- the checker --------------------------------------------------------------------
+def _result(graph, explainer, sccs, history):
+    return {"valid?": not sccs, "scc-count": len(sccs),
+            "cycles": [explain_scc(graph, explainer, c, history) for c in sccs[:A.CY_SCC_CAP]]}
+
+
+def check_host(analyze_fn, history):
+    """The checker's map on the host: cycle.clj:911-934."""
+    history = [op for op in _indexed(history) if op.get("process") != "nemesis"]
+    try:
+        graph, explainer = analyze_fn(history)
+    except IllegalArgument as e:              # positions in the filtered history -> the ops' own :index
+        e.row, e.rows = history[e.row]["index"], [history[j]["index"] for j in e.rows]
+        raise
+    except IllegalHistory as e:
+        raise IllegalHistory(e.cause, history[e.row]["index"]) from None
+    sccs = sccs_of(scc_labels(graph.n, graph.edges))
+    return _result(graph, explainer, sccs, history)
+
+
+def _explainer_for(analyze_fn, history):
+    table = {process_graph: ProcessExplainer, wr_graph: WRExplainer}
+    parts = getattr(analyze_fn, "parts", (analyze_fn,))
+    out = []
+    for p in parts:
+        if p is realtime_graph:
+            out.append(RealtimeExplainer([op for op in history if op.get("process") != "nemesis"]))
+        elif p in table:
+            out.append(table[p]())
+        else:
+            out.append(_explainer_for(p, history))
+    return out[0] if len(out) == 1 and not hasattr(analyze_fn, "parts") else CombinedExplainer(out)
+
+
+def raise_unknown(res, history, keys):
+    """What the reference raises for a JH_UNKNOWN result."""
+    cause, row = res["cause"], res["unknown_row"]
+    if cause == A.CAUSE_MULTIPLE_WRITES:
+        k, v = keys[res["unknown_key"]], (None if res["unknown_value"] == A.NIL else res["unknown_value"])
+        e = IllegalArgument(f"Key {pr_str(k)} had value {pr_str(v)} written by more than one op: "
+                            f"{[history[j] for j in res['unknown_rows']]!r}")
+        e.row, e.key, e.value, e.rows = row, k, v, list(res["unknown_rows"])
+        raise e
+    raise IllegalHistory(A.CAUSES[cause], row)
+
+
+class CycleChecker:
+    """(cycle/checker analyze-fn). path: 0 auto, 1 on-chip, 2 global tier.
+    device=False keeps everything on the host."""
+
+    def __init__(self, analyze_fn, path=A.CY_PATH_AUTO, device=True):
+        self.analyze_fn, self.path, self.device = analyze_fn, path, device
+
+    def check(self, test, history, opts):
+        from . import _native
+        from . import checker as K
+        mask = getattr(self.analyze_fn, "analyzers", None)
+        history = _indexed(history)
+        if not self.device or not mask:
+            return check_host(self.analyze_fn, history)
+        try:
+            cols = encode(history, txns=bool(mask & A.CY_WR))
+        except (TypeError, ValueError):
+            return check_host(self.analyze_fn, history)
+        try:
+            ctx = K._ctx()
+            res = ctx.check_cycle(cols, mask, self.path)
+            if res["valid"] == A.INVALID:
+                res = ctx.check_cycle(cols, mask, self.path, edge_cap=sum(res["edge_count"]))
+        except _native.JhError as e:
+            if e.code != A.JH_EUNSUPPORTED:
+                raise
+            return check_host(self.analyze_fn, history)
+        if res["valid"] == A.UNKNOWN:
+            raise_unknown(res, history, cols.keys)
+        sccs = res["sccs"]
+        if not sccs:
+            return {"valid?": True, "scc-count": 0, "cycles": []}
+        members = set(v for c in sccs for v in c)
+        e = res["edges"]
+        e = e[np.isin(e[:, 0], list(members)) & np.isin(e[:, 1], list(members))]
+        out = _result(Graph(cols.n, e), _explainer_for(self.analyze_fn, history), sccs, history)
+        out["scc-count"] = int(res["scc_count"])
+        return out
+
+
+def checker(analyze_fn, path=A.CY_PATH_AUTO, device=True):
+    return CycleChecker(analyze_fn, path, device)

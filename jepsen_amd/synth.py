@@ -790,3 +790,79 @@ def causal_reverse_columns_to_ops(cols):
     keyed rows; jepsen_amd/causal_reverse.py decode)."""
     from . import causal_reverse
     return causal_reverse.decode(cols)
+
+
+def txn_cycle_history(n_ops=1000, n_procs=10, n_keys=100, anomalies=0, p_info=0.02, seed=0):
+    """A transactional history for jepsen.tests.cycle as Columns (include/jh.h,
+    "Cycle txns"): n_ops txns of n_procs processes, each one external read and
+    one write ([:r k v] [:w k' v'], written values unique per key), taking
+    effect at their invocation, so a reader may complete before its writer does
+    (back edges) while wr + realtime stay acyclic. A crashed (:info) txn's
+    process is replaced, as jepsen replaces it. anomalies: that many :ok txns
+    are made to read what a txn invoked after their completion writes (a cycle
+    through realtime edges each)."""
+    from . import _abi as A
+    rng = np.random.default_rng(seed)
+    cur = np.full(n_keys, A.NIL, np.int64)
+    nxt = np.zeros(n_keys, np.int64)
+    proc, typ, val, val2, aux = [], [], [], [], []
+    open_ = {}                                   # slot -> (process id, mops)
+    pid = list(range(n_procs))
+    txn_rows = []                                # (invoke row, completion row, type, aux index)
+    started = 0
+    slots = rng.integers(n_procs, size=4 * n_ops + 4 * n_procs)
+    keys = rng.integers(n_keys, size=(n_ops, 2))
+    infos = rng.random(n_ops) < p_info
+    at = 0
+    while started < n_ops or open_:
+        s = int(slots[at % len(slots)])
+        at += 1
+        if s in open_:
+            p, mi, row_i, t_i = open_.pop(s)
+            t = A.TYPE_INFO if infos[t_i] else A.TYPE_OK
+            txn_rows.append((row_i, len(proc), t, mi))
+            proc.append(p); typ.append(t); val.append(mi); val2.append(2)
+            if t == A.TYPE_INFO:
+                pid[s] += n_procs
+        elif started < n_ops:
+            kr, kw = int(keys[started, 0]), int(keys[started, 1])
+            nxt[kw] += 1
+            mi = len(aux) // 3
+            aux += [A.F_READ, kr, int(cur[kr]), A.F_WRITE, kw, int(nxt[kw])]
+            cur[kw] = nxt[kw]
+            open_[s] = (pid[s], mi, len(proc), started)
+            proc.append(pid[s]); typ.append(A.TYPE_INVOKE); val.append(A.NIL); val2.append(0)
+            started += 1
+    oks = [t for t in txn_rows if t[2] == A.TYPE_OK]
+    inv_rows = np.asarray([t[0] for t in oks], np.int64)
+    for _ in range(anomalies):
+        if len(oks) < 2:
+            break
+        a = oks[int(rng.integers(len(oks) // 2))]
+        later = np.nonzero(inv_rows > a[1])[0]
+        if len(later) == 0:
+            continue
+        b = oks[int(later[min(int(rng.integers(8)), len(later) - 1)])]
+        aux[3 * a[3] + 1], aux[3 * a[3] + 2] = aux[3 * b[3] + 4], aux[3 * b[3] + 5]
+    n = len(proc)
+    return Columns(n=n, process=np.asarray(proc, np.int64), type=np.asarray(typ, np.int64),
+                   f=np.full(n, A.F_FIRST_INTERNED, np.int64), key=np.full(n, -1, np.int64),
+                   value=np.asarray(val, np.int64), value2=np.asarray(val2, np.int64), n_keys=0,
+                   aux=np.asarray(aux if aux else [0, 0, 0], np.int64), keys=list(range(n_keys)), f_names=["txn"])
+
+
+def txn_cycle_columns_to_ops(cols):
+    """Op maps of txn_cycle_history's Columns: completions carry their txn as
+    [f k v] micro-ops, invocations nil."""
+    from . import _abi as A
+    out = []
+    for i in range(cols.n):
+        v = None
+        if int(cols.type[i]) != A.TYPE_INVOKE and int(cols.value2[i]) > 0:
+            s, c = int(cols.value[i]), int(cols.value2[i])
+            v = [["r" if int(cols.aux[3 * j]) == A.F_READ else "w", int(cols.aux[3 * j + 1]),
+                  None if int(cols.aux[3 * j + 2]) == A.NIL else int(cols.aux[3 * j + 2])] for j in range(s, s + c)]
+        p = int(cols.process[i])
+        out.append({"process": p if p >= 0 else "nemesis", "type": ("invoke", "ok", "fail", "info")[int(cols.type[i])],
+                    "f": "txn", "value": v})
+    return out
