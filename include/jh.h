@@ -92,6 +92,15 @@
  * JH_F_WRITE, k an int64 the caller interned and v an int64 or JH_NIL; n_aux is
  * a multiple of 3. A nil :value is value = JH_NIL, value2 = 0. Rows of other
  * types are not read.
+ *
+ * Append txns (jh_check_cycle with JH_CY_APPEND): every non-nemesis row of every
+ * type carries its txn: value = the aux word index of its first micro-op and
+ * value2 = its number of micro-ops (a nil :value is JH_NIL, 0). Micro-op j is
+ * the four words aux[value + 4j .. +4) = [f, k, a, b]. f = JH_F_READ: a = the aux
+ * word index of the read's first element and b = its number of elements (nil
+ * and [] are b = 0, and then a is not looked at). f = JH_F_APPEND: a = the
+ * element, b = 0. Elements are int64 and never JH_NIL; k is dense,
+ * 0 <= k < n_keys.
  */
 #ifndef JH_H
 #define JH_H
@@ -882,16 +891,61 @@ int jh_check_causal_reverse(jh_ctx *ctx, const jh_history *h, const jh_causal_re
  *                  unknown_value = that row's first such pair in micro-op order,
  *                  unknown_rows = its two smallest writer rows. A (k, v) written
  *                  twice and never read externally is not an error.
+ *  JH_CY_APPEND    appends-and-reads-graph, cycle.clj:381-699, txns encoded as
+ *                  "Append txn encoding" below; not together with JH_CY_WR
+ *                  (JH_EINVAL: the two read the txn columns differently and share
+ *                  edge_count[2]). A position is (row, micro-op index); "first"
+ *                  is the smallest position, the order of the reference's
+ *                  reduce-mops. The checks run in this order and the first that
+ *                  fires is the result:
+ *                  unique appends (:invoke rows): the first [:append k v] whose
+ *                  (k, v) an earlier :invoke micro-op appended (one of the same
+ *                  txn included) -> JH_CAUSE_DUPLICATE_APPENDS.
+ *                  no dups (rows of every type): the first read that holds an
+ *                  element twice -> JH_CAUSE_DUPLICATE_ELEMENTS.
+ *                  From here on only :ok and :info rows count. total order:
+ *                  every read of k must be a prefix of L_k, k's longest read
+ *                  (the first one of that length); nil and [] are both the
+ *                  empty read. A key with a read that is not -> JH_CAUSE_NO_
+ *                  TOTAL_ORDER. The writer of (k, v) is the last :ok / :info
+ *                  row appending it. Edges, for every micro-op of every :ok /
+ *                  :info row r, never from a row to itself:
+ *                   wr  [:r k v], v not empty: writer(k, last v) -> r.
+ *                   ww  [:append k v], v at position i > 0 of L_k:
+ *                       writer(k, L_k[i-1]) -> r.
+ *                   rw  the same append, i >= 0: q -> r for every read micro-op
+ *                       of k of length i on an :ok / :info row q (once per such
+ *                       micro-op: repeats are counted in edge_count[2]).
+ *                  An append whose value stands in no read gives nothing. A wr
+ *                  or ww writer that does not exist (the element came from a
+ *                  :fail op, or from nothing) -> JH_CAUSE_NO_WRITER at the first
+ *                  such micro-op (the reference's assert).
+ *                  cause                 valid       unknown_row  unknown_rows[0]  unknown_key  unknown_value
+ *                  13 DUPLICATE_APPENDS  JH_UNKNOWN  row          micro-op index   k            v
+ *                  14 DUPLICATE_ELEMENTS JH_INVALID  row          micro-op index   k            the read's first element, in
+ *                                                    list order, that equals an earlier one
+ *                  15 NO_TOTAL_ORDER     JH_INVALID  the smallest row with a read of unknown_key that is no prefix of
+ *                                                    its L_k; unknown_rows[0] = the number of bad keys, unknown_key =
+ *                                                    the smallest bad key, unknown_value = JH_NIL
+ *                  16 NO_WRITER          JH_UNKNOWN  row          micro-op index   k            the element nobody appended
+ *                  unknown_rows[1] is -1 in all four. JH_INVALID with cause == 0
+ *                  keeps meaning "SCCs".
  *  extra edges     opts->extra_src / extra_dst / n_extra: host int64 history rows
- *                  (monotonic-key and append edges are built by the shim).
- * With several unknown causes the first of: double invoke, orphan, unmatched
- * invoke, multiple writes is reported; edges and SCCs are not computed then.
+ *                  (monotonic-key edges are built by the shim).
+ * With several causes the first of: double invoke, orphan, unmatched invoke,
+ * multiple writes, then 13, 14, 15, 16 is reported; edges and SCCs are not
+ * computed then (scc_count = 0, labels_out all -1).
  *
  * Txn encoding (JH_CY_WR only): an :ok txn row has value = the index of its
  * first micro-op and value2 = its number of micro-ops; micro-op j is the triple
  * aux[3*(value+j) .. +3) = [f, k, v], f = JH_F_READ / JH_F_WRITE, k an int64 the
  * caller interned, v an int64 or JH_NIL; n_aux is a multiple of 3. A nil :value
  * is value = JH_NIL, value2 = 0. Rows of other types are not read.
+ *
+ * Append txn encoding (JH_CY_APPEND only): see "Append txns" at the top. With
+ * it edge_count[2] = the number of link calls of the reference (repeats are
+ * counted, pairs of a row with itself are not) and entries = micro-ops scanned
+ * plus read elements scanned.
  *
  * SCCs. An edge with dst < src is a back edge; every cycle holds one, and the
  * row intervals [dst, src] of the back edges, merged where they overlap, are
@@ -914,7 +968,13 @@ int jh_check_causal_reverse(jh_ctx *ctx, const jh_history *h, const jh_causal_re
  *
  * JH_EUNSUPPORTED (the shim falls back): a micro-op f other than read / write; a
  * txn of more than JH_CY_MAX_MOPS micro-ops; more than 2^31 - 2 vertices or
- * edges; a region past the work cap. JH_EINVAL: a txn range leaving
+ * edges; a region past the work cap; with JH_CY_APPEND also an f other than
+ * read / append, more than 2^31 - 2 records, and a read that needs the direct
+ * duplicate check (it stands on an :invoke / :fail row, or is no prefix of its
+ * L_k) and is longer than JH_CY_AP_DIRECT_READ elements. JH_EINVAL with
+ * JH_CY_APPEND: a micro-op or element range leaving [0, n_aux), a negative
+ * count, a key outside [0, n_keys), an element equal to JH_NIL, JH_CY_APPEND |
+ * JH_CY_WR. JH_EINVAL otherwise: a txn range leaving
  * [0, n_aux / 3), a negative count, n_aux % 3 != 0, an edge endpoint outside
  * [0, n), analyzers == 0 with no extra edges, a :type outside 0..3, path 1
  * forced with a region of more than JH_CY_LDS_VERTICES vertices. */
@@ -922,6 +982,13 @@ int jh_check_causal_reverse(jh_ctx *ctx, const jh_history *h, const jh_causal_re
 #define JH_CY_PROCESS  1
 #define JH_CY_REALTIME 2
 #define JH_CY_WR       4
+#define JH_CY_APPEND   16                /* (8 is not an analyzer) */
+#define JH_F_APPEND    7                 /* micro-op f of an append txn */
+#define JH_CY_AP_DIRECT_READ 4096        /* elements of a read the direct duplicate check takes (a cap on a slow path) */
+#define JH_CAUSE_DUPLICATE_APPENDS  13   /* cycle, JH_CY_APPEND: see the table above */
+#define JH_CAUSE_DUPLICATE_ELEMENTS 14
+#define JH_CAUSE_NO_TOTAL_ORDER     15
+#define JH_CAUSE_NO_WRITER          16
 #define JH_CY_LDS_VERTICES 2048          /* vertices of a region of the on-chip tier (16 B each) */
 #define JH_CY_MAX_MOPS 64                /* micro-ops per txn */
 #define JH_CY_WORK_MULT 64               /* work cap of a region: this * (vertices + edges) edge visits */
@@ -939,11 +1006,11 @@ typedef struct jh_cycle_result {
     int32_t path;                  /* 1: every region on chip, 2: some region in the global tier, 0: no region */
     int32_t pad;
     int64_t scc_count, scc_vertices;
-    int64_t edge_count[4];         /* process, realtime, wr, extra (jh_scc: all in [3]); self-loops and repeats counted */
+    int64_t edge_count[4];         /* process, realtime, wr or append, extra (jh_scc: all in [3]); self-loops and repeats counted */
     int64_t back_edges;
     int64_t regions, max_region, global_regions;   /* regions of >= 2 vertices; the largest one's vertices */
     int64_t unknown_row, unknown_key, unknown_value, unknown_rows[2];   /* -1 / JH_NIL / JH_NIL / -1 when unused */
-    int64_t entries;               /* micro-ops scanned */
+    int64_t entries;               /* micro-ops scanned (JH_CY_APPEND: plus read elements scanned) */
     double device_ms;
 } jh_cycle_result;
 

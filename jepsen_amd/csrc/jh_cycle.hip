@@ -17,8 +17,11 @@
 //                     realtime: a reverse min-scan gives R(c), a prefix count of
 //                     invokes the number of edges, an exclusive sum their place,
 //                     k_cy_rt_fill one thread per edge.
+//                     appends-and-reads-graph (JH_CY_APPEND, in place of wr) is
+//                     jh_cycle_append.hip: append_plan verifies and sizes,
+//                     append_fill writes the wr / ww / rw slots.
 //                     Builders leave holes (~0) where a slot has no edge; one
-//                     select compacts process | realtime | wr | extra.
+//                     select compacts process | realtime | wr | append | extra.
 //   2. regions        reach[dst] = max src over the back edges (atomicMax), an
 //                     inclusive max-scan, boundary flags and their prefix sum:
 //                     the regions of >= 2 vertices as [start, end] row intervals.
@@ -34,20 +37,15 @@
 //                     with them in HBM, indexed by row.
 //   4. results        counts; the SCCs ordered by (size, smallest row) by two
 //                     radix sorts (roots, members).
-#include "jh_internal.h"
-#include <hipcub/hipcub.hpp>
+#include "cycle_common.h"
 #include <algorithm>
 #include <vector>
 
 namespace {
-constexpr int T_INVOKE = 0, T_OK = 1, T_FAIL = 2;
-constexpr unsigned long long HOLE = ~0ULL, NONE = ~0ULL;
-constexpr long long Y_MAX = 0x7ffffffeLL;
 constexpr int CAP = JH_CY_LDS_VERTICES;
 constexpr int RT = 256;                       // threads of a region's workgroup
 constexpr int REMOVED = 0x7fffffff;           // status: out of the region's graph
 constexpr int BIG = 0x7fffffff;
-typedef unsigned long long u64;
 
 struct YMeta {
     unsigned bad_range, unsup_f, unsup_mops, bad_type, over_work, pad;
@@ -65,8 +63,6 @@ __global__ void k_cy_meta_init(YMeta *m) {
     m->unknown_rows[0] = m->unknown_rows[1] = -1;
 }
 
-__device__ __forceinline__ u64 pack(int64_t s, int64_t d) { return ((u64)s << 32) | (u64)(uint32_t)d; }
-#define CY_LOOP(i, cnt) for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < (cnt); i += (int64_t)gridDim.x * blockDim.x)
 
 // ---------------------------------------------------------------------------
 // 1a. rows: the sort key by process, :type check, the first :ok row
@@ -199,7 +195,7 @@ __global__ void __launch_bounds__(256) k_cy_txn(const int64_t *__restrict__ proc
                     if (FILL) {
                         const int64_t v = t[3 * j + 2];
                         wk[wo + nw] = k; wv[wo + nw] = v; wrow[wo + nw] = (int32_t)i;
-                        whash[wo + nw] = jh_mix64((u64)k * 0x9e3779b97f4a7c15ULL + jh_mix64((u64)v));
+                        whash[wo + nw] = cy_hash(k, v);
                         widx[wo + nw] = (uint32_t)(wo + nw);
                     }
                     nw++;
@@ -219,7 +215,7 @@ __device__ __forceinline__ int cy_writers(const u64 *__restrict__ shash, const u
                                           const int64_t *__restrict__ wk, const int64_t *__restrict__ wv,
                                           const int32_t *__restrict__ wrow, long long W, int64_t k, int64_t v, int *w0,
                                           int *w1) {
-    const u64 h = jh_mix64((u64)k * 0x9e3779b97f4a7c15ULL + jh_mix64((u64)v));
+    const u64 h = cy_hash(k, v);
     long long lo = 0, hi = W;
     while (lo < hi) {
         const long long mid = (lo + hi) >> 1;
@@ -560,20 +556,11 @@ int bits_of(u64 x) {
     return b;
 }
 
-char *tmp(jh_ctx *ctx, size_t bytes) { return ctx->ws<char>(WS_CY_TMP, bytes); }
-
 YMeta read_meta(const YMeta *m, hipStream_t st) {
     YMeta h;
     HIP_TRY(hipMemcpyAsync(&h, m, sizeof h, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return h;
-}
-
-template <class T>
-void excl_sum(jh_ctx *ctx, const T *in, T *out, int64_t cnt, hipStream_t st) {
-    size_t tb = 0;
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, in, out, (int)cnt, st));
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp(ctx, tb), tb, in, out, (int)cnt, st));
 }
 
 // the words of `in` that are not holes, in order; returns their number
@@ -587,12 +574,6 @@ long long select_edges(jh_ctx *ctx, const u64 *in, u64 *out, long long cnt, hipS
     HIP_TRY(hipMemcpyAsync(&got, d_n, sizeof got, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return got;
-}
-
-void sort_keys(jh_ctx *ctx, const u64 *in, u64 *out, long long cnt, int end_bit, hipStream_t st) {
-    size_t tb = 0;
-    HIP_TRY(hipcub::DeviceRadixSort::SortKeys(nullptr, tb, in, out, (int)cnt, 0, end_bit, st));
-    HIP_TRY(hipcub::DeviceRadixSort::SortKeys(tmp(ctx, tb), tb, in, out, (int)cnt, 0, end_bit, st));
 }
 
 void init_result(jh_cycle_result *res) {
@@ -850,19 +831,26 @@ void cycle_check(jh_ctx *ctx, const jh_history *dh, const jh_cycle_opts *opts, j
         HIP_TRY(hipMemcpyAsync(&n_rt, rt_off + n, sizeof n_rt, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
     }
+    // appends-and-reads: the verification passes and the number of its slots (jh_cycle_append.hip)
+    AppendPlan ap;
+    if (an & JH_CY_APPEND) {
+        ap = append_plan(ctx, dh, res, st);
+        if (ap.cause) { timer.stop(); return; }
+    }
     long long R = 0, W = 0;
     if (an & JH_CY_WR) {
         HIP_TRY(hipMemcpyAsync(&R, ro + n, sizeof R, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipMemcpyAsync(&W, wo + n, sizeof W, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
     }
-    const long long n_raw = n_proc_slots + n_rt + R + (long long)extra.size();
+    const long long n_raw = n_proc_slots + n_rt + R + ap.slots + (long long)extra.size();
     if (n_rt > Y_MAX || R > Y_MAX || W > Y_MAX || n_raw > Y_MAX)
         throw_jh(JH_EUNSUPPORTED, "cycle: more than 2^31 - 2 vertices or edges");
 
-    // every builder's slots in one buffer: process | realtime | wr | extra
+    // every builder's slots in one buffer: process | realtime | wr | append | extra
     u64 *raw = ctx->ws<u64>(WS_CY_RAW, n_raw);
-    u64 *raw_rt = raw + n_proc_slots, *raw_wr = raw_rt + n_rt, *raw_x = raw_wr + R;
+    u64 *raw_rt = raw + n_proc_slots, *raw_wr = raw_rt + n_rt, *raw_ap = raw_wr + R, *raw_x = raw_ap + ap.slots;
+    const long long ap_links = (an & JH_CY_APPEND) ? append_fill(ctx, ap, raw_ap, st) : 0;
     if (n_proc_slots) HIP_TRY(hipMemcpyAsync(raw, proc_raw, sizeof(u64) * n, hipMemcpyDeviceToDevice, st));
     if (n_rt > 0) k_cy_rt_fill<<<grid_for(n_rt, 256, 4096), 256, 0, st>>>(rt_off, ip, icomp, n, n_rt, raw_rt);
     if (R > 0) {
@@ -890,7 +878,7 @@ void cycle_check(jh_ctx *ctx, const jh_history *dh, const jh_cycle_opts *opts, j
     }
     res->edge_count[0] = (int64_t)mh.edges[0];
     res->edge_count[1] = n_rt;
-    res->edge_count[2] = (int64_t)mh.edges[2];
+    res->edge_count[2] = (an & JH_CY_APPEND) ? ap_links : (int64_t)mh.edges[2];
     u64 *edges = ctx->ws<u64>(WS_CY_EDGES, n_raw);
     const long long E = select_edges(ctx, raw, edges, n_raw, st);
     scc_core(ctx, n, edges, E, opts->path, res, out, m, st);

@@ -133,6 +133,7 @@ enum WsSlot {
     WS_CY_META, WS_CY_TMP, WS_CY_PKEY, WS_CY_PROW, WS_CY_COMP, WS_CY_REV, WS_CY_IP, WS_CY_ICOMP, WS_CY_CNT,
     WS_CY_TXN, WS_CY_REC, WS_CY_HASH, WS_CY_HIDX, WS_CY_RAW, WS_CY_EDGES, WS_CY_REACH, WS_CY_BS, WS_CY_REG, WS_CY_SEL,
     WS_CY_FWD, WS_CY_BWD, WS_CY_CSR, WS_CY_STATE, WS_CY_LABEL, WS_CY_SIZE, WS_CY_KEYS, WS_CY_VALS,
+    WS_CY_AP_META, WS_CY_AP_ROWS, WS_CY_AP_RECS, WS_CY_AP_LONGEST,
     WS_COUNT
 };
 
@@ -226,3 +227,13 @@ void scc_check(jh_ctx *ctx, int64_t n, const int64_t *src, const int64_t *dst, i
                const jh_cycle_opts *opts, jh_cycle_result *res, const CycleOut &out, hipStream_t stream);
 void cycle_check(jh_ctx *ctx, const jh_history *dh, const jh_cycle_opts *opts, jh_cycle_result *res,
                  const CycleOut &out, hipStream_t stream);
+// appends-and-reads-graph (jh_cycle_append.hip). append_plan runs the verification passes and sizes the
+// edge slots (cause != 0: res holds the cause's fields and nothing more is to be done); append_fill writes
+// plan.slots packed words, holes included, and returns the number of link calls
+struct AppendPlan {
+    int cause = 0;
+    long long reads = 0, appends = 0, rw = 0, slots = 0;
+    alignas(8) unsigned char state[640] = {};   // the builder's device arrays between the two calls
+};
+AppendPlan append_plan(jh_ctx *ctx, const jh_history *dh, jh_cycle_result *res, hipStream_t stream);
+long long append_fill(jh_ctx *ctx, const AppendPlan &plan, unsigned long long *raw, hipStream_t stream);

@@ -10,10 +10,12 @@ every SCC of more than one op as an anomaly:
 
 Vertices are positions in the history the analyzer was given (the checker gives
 every op an "index" first, so they are history rows). The module's own analyzers
-(process_graph, realtime_graph, wr_graph and their `combine`) carry a mask of
-JH_CY_* bits: a checker over them makes ONE jh_check_cycle call when the values
-encode (include/jh.h, "Cycle txns": keys are interned, values must be longs or
-nil) and runs the host implementation otherwise. The host implementation is the
+(process_graph, realtime_graph, wr_graph, appends_and_reads_graph and their
+`combine`) carry a mask of JH_CY_* bits: a checker over them makes ONE
+jh_check_cycle call when the values encode (include/jh.h, "Cycle txns" and
+"Append txns": keys are interned, values and list elements must be longs) and
+runs the host implementation otherwise (also for wr_graph combined with
+appends_and_reads_graph, which the device refuses). The host implementation is the
 numpy closed forms below; tests/cycle_ref.py holds the literal transcriptions
 they are tested against. Explanations run on the host over the at most 8
 reported SCCs.
@@ -30,6 +32,7 @@ from . import history as H
 
 I64_MIN, I64_MAX = -(1 << 63), (1 << 63) - 1
 READ_FS, WRITE_FS = ("r", "read"), ("w", "write")
+APPEND_F = "append"
 
 
 class IllegalArgument(ValueError):
@@ -357,6 +360,11 @@ class WRExplainer:
         return None
 
 
+class AppendsAndReadsExplainer:
+    def explain_pair(self, a, b):
+        return "something something"
+
+
 class CombinedExplainer:
     def __init__(self, explainers):
         self.explainers = list(explainers)
@@ -392,6 +400,7 @@ def wr_graph(history):
 
 
 process_graph.analyzers, realtime_graph.analyzers, wr_graph.analyzers = A.CY_PROCESS, A.CY_REALTIME, A.CY_WR
+# (appends_and_reads_graph, defined with its closed forms below, carries A.CY_APPEND)
 
 
 def combine(*analyzers):
@@ -495,6 +504,285 @@ def encode(history, txns=True):
                      keys=list(key_ids))
 
 
+# -- appends-and-reads-graph (cycle.clj:381-699) ---------------------------------------
+class AnalysisMap(Exception):
+    """throw+ of a map with :valid?: the checker returns the map as its result."""
+
+    def __init__(self, m):
+        super().__init__(m.get("message"))
+        self.map = m
+
+
+def encode_append(history, strict=True):
+    """Op maps -> Columns (include/jh.h, "Append txns"): every non-nemesis row
+    carries its txn as [f, k, a, b] words, the reads' elements behind them in
+    the same aux array, keys dense in first-appearance order. TypeError for an
+    f outside r / append, a read value that is no list / nil, an element that is
+    no long or is nil. strict=False (the host analyzer): elements are interned,
+    so anything hashable stands (only their equality is used)."""
+    history = list(history)
+    n = len(history)
+    proc, typ = _encode_rows(history)
+    val, val2 = np.full(n, A.NIL, np.int64), np.zeros(n, np.int64)
+    words, elems, key_ids, interned = [], [], {}, {}
+
+    def elem(x):
+        if strict:
+            if x is None or _long(x) == A.NIL:
+                raise TypeError(f"cycle: element {x!r} has no encoding")
+            return int(x)
+        return interned.setdefault(x, len(interned))
+
+    for i, op in enumerate(history):
+        v = op.get("value")
+        if op.get("process") == "nemesis" or v is None:
+            continue
+        if not isinstance(v, (list, tuple)):
+            raise TypeError(f"cycle: a txn of {v!r}")
+        val[i], val2[i] = len(words), len(v)
+        for mop in v:
+            f, k, x = mop
+            kid = key_ids.setdefault(k, len(key_ids))
+            if f in READ_FS:
+                if x is not None and not isinstance(x, (list, tuple)):
+                    raise TypeError(f"cycle: a read of {x!r}")
+                words += [A.F_READ, kid, -1 - len(elems), len(x or ())]       # the offset: placed below
+                elems += [elem(e) for e in (x or ())]
+            elif f == APPEND_F:
+                words += [A.F_APPEND, kid, elem(x), 0]
+            else:
+                raise TypeError(f"cycle: a micro-op {f!r}")
+    aux = np.asarray(words + elems, np.int64) if words else np.zeros(0, np.int64)
+    w = aux[:len(words)].reshape(-1, 4)
+    reads = w[:, 0] == A.F_READ
+    w[reads, 2] = len(words) + (-1 - w[reads, 2])
+    return H.Columns(n=n, process=proc, type=typ, f=np.full(n, A.F_FIRST_INTERNED, np.int64), key=None, value=val,
+                     value2=val2, n_keys=len(key_ids), aux=aux if len(aux) else np.zeros(4, np.int64)[:0], keys=list(key_ids))
+
+
+class _Mops:
+    """The read and append records of encoded append txns, in (row, micro-op) order."""
+
+    def __init__(self, cols):
+        proc, typ, aux = np.asarray(cols.process), np.asarray(cols.type), np.asarray(cols.aux, np.int64)
+        val2 = np.asarray(cols.value2)
+        rows = np.nonzero((proc != -1) & (val2 > 0))[0]
+        cnt = val2[rows]
+        mrow = np.repeat(rows, cnt)
+        mj = np.arange(int(cnt.sum())) - np.repeat(np.cumsum(cnt) - cnt, cnt)
+        base = np.repeat(np.asarray(cols.value)[rows], cnt) + 4 * mj
+        f = aux[base] if len(base) else np.zeros(0, np.int64)
+        pick = lambda sel, off: aux[base[sel] + off] if len(base) else np.zeros(0, np.int64)
+        r, a = f == A.F_READ, f == A.F_APPEND
+        self.aux, self.n_keys = aux, int(cols.n_keys)
+        self.rrow, self.rmop, self.rk, self.roff, self.rlen = mrow[r], mj[r], pick(r, 1), pick(r, 2), pick(r, 3)
+        self.arow, self.amop, self.ak, self.av = mrow[a], mj[a], pick(a, 1), pick(a, 2)
+        self.rcnt = np.isin(typ[self.rrow], (A.TYPE_OK, A.TYPE_INFO))
+        self.atype = typ[self.arow]
+        self.entries = int(len(f) + self.rlen.sum())
+
+    def elements(self, reads):
+        """(read, place, element) of every element of the reads `reads` (record indices)."""
+        ln = self.rlen[reads]
+        rid = np.repeat(reads, ln)
+        place = np.arange(int(ln.sum())) - np.repeat(np.cumsum(ln) - ln, ln)
+        return rid, place, self.aux[self.roff[rid] + place]
+
+    def longest(self):
+        """lrec[k] = the record of k's longest counted read (the first of that length), -1: none."""
+        c = np.nonzero(self.rcnt)[0]
+        o = c[np.lexsort((c, -self.rlen[c], self.rk[c]))]
+        first = np.ones(len(o), bool)
+        first[1:] = self.rk[o[1:]] != self.rk[o[:-1]]
+        lrec = np.full(self.n_keys, -1, np.int64)
+        lrec[self.rk[o[first]]] = o[first]
+        return lrec
+
+
+def duplicate_append(m):
+    """cycle.clj:407-426: (row, micro-op) of the first :invoke append whose (k, v)
+    an earlier :invoke micro-op appended, or None."""
+    idx = np.nonzero(m.atype == A.TYPE_INVOKE)[0]
+    if len(idx) < 2:
+        return None
+    o = idx[np.lexsort((idx, m.av[idx], m.ak[idx]))]
+    again = (m.ak[o[1:]] == m.ak[o[:-1]]) & (m.av[o[1:]] == m.av[o[:-1]])
+    if not again.any():
+        return None
+    x = int(o[1:][again].min())
+    return int(m.arow[x]), int(m.amop[x])
+
+
+def duplicate_read(m):
+    """cycle.clj:499-519: (row, micro-op) of the first read, on a row of any
+    type, that holds an element twice, or None."""
+    rid, place, ev = m.elements(np.nonzero(m.rlen > 1)[0])
+    if len(rid) == 0:
+        return None
+    o = np.lexsort((ev, rid))
+    again = (rid[o[1:]] == rid[o[:-1]]) & (ev[o[1:]] == ev[o[:-1]])
+    if not again.any():
+        return None
+    x = int(rid[o[1:]][again].min())
+    return int(m.rrow[x]), int(m.rmop[x])
+
+
+def bad_order_keys(m):
+    """cycle.clj:438-497 in closed form: {key id: smallest row with a counted read
+    of it that is no prefix of the key's longest counted read}."""
+    lrec = m.longest()
+    rid, place, ev = m.elements(np.nonzero(m.rcnt & (m.rlen > 0))[0])
+    if len(rid) == 0:
+        return {}
+    bad = rid[ev != m.aux[m.roff[lrec[m.rk[rid]]] + place]]
+    out = {}
+    for x in np.unique(bad).tolist():
+        out.setdefault(int(m.rk[x]), int(m.rrow[x]))
+    return out
+
+
+def append_edges(m):
+    """cycle.clj:641-699 in closed form over the records of a history that passed
+    the three checks: the (E, 2) wr, ww and rw edges, one per link call (repeats
+    kept, a row never links to itself). IllegalHistory("no-writer") at the first
+    micro-op whose wr / ww writer does not exist; .key / .value name the pair."""
+    lrec = m.longest()
+    ca = np.nonzero(np.isin(m.atype, (A.TYPE_OK, A.TYPE_INFO)))[0]
+    cr = np.nonzero(m.rcnt)[0]
+    # L_k's elements, key after key (lstart[k] = where L_k starts)
+    keys = np.nonzero(lrec >= 0)[0]
+    _, lj, lv = m.elements(lrec[keys])
+    lk = np.repeat(keys, m.rlen[lrec[keys]])
+    lstart = np.zeros(m.n_keys + 1, np.int64)
+    lstart[keys + 1] = m.rlen[lrec[keys]]
+    lstart = np.cumsum(lstart)
+    nz = cr[m.rlen[cr] > 0]
+    last = m.aux[m.roff[nz] + m.rlen[nz] - 1]
+    uniq = np.unique(np.concatenate([m.av[ca], lv, last]))
+
+    def pair(k, v):                          # (k, v) as one word that compares like the pair
+        return k * max(len(uniq), 1) + np.searchsorted(uniq, v)
+
+    def lookup(table_keys, table_vals, q):   # table_keys ascending; -1 where q is not in it
+        if len(table_keys) == 0:
+            return np.full(len(q), -1, np.int64)
+        at = np.minimum(np.searchsorted(table_keys, q), len(table_keys) - 1)
+        return np.where(table_keys[at] == q, table_vals[at], -1)
+    # writers: the last counted append of (k, v)
+    wkey = pair(m.ak[ca], m.av[ca])
+    o = np.lexsort((ca, wkey))
+    lastof = np.ones(len(o), bool)
+    lastof[:-1] = wkey[o[1:]] != wkey[o[:-1]]
+    wkeys, wrows = wkey[o[lastof]], m.arow[ca[o[lastof]]]
+    # the counted appends' positions in L_k
+    lkey = pair(lk, lv)
+    lo = np.argsort(lkey, kind="stable")
+    pos = lookup(lkey[lo], lj[lo], wkey)
+    missing, edges = [], []
+    # wr
+    w = lookup(wkeys, wrows, pair(m.rk[nz], last))
+    missing += [(int(m.rrow[x]), int(m.rmop[x]), int(m.rk[x]), int(e)) for x, e in zip(nz[w < 0].tolist(), last[w < 0].tolist())]
+    keep = (w >= 0) & (w != m.rrow[nz])
+    edges.append(np.stack([w[keep], m.rrow[nz][keep]], axis=1))
+    # ww
+    xs = ca[pos > 0]
+    prev = lv[lstart[m.ak[xs]] + pos[pos > 0] - 1]
+    w = lookup(wkeys, wrows, pair(m.ak[xs], prev))
+    missing += [(int(m.arow[x]), int(m.amop[x]), int(m.ak[x]), int(e)) for x, e in zip(xs[w < 0].tolist(), prev[w < 0].tolist())]
+    keep = (w >= 0) & (w != m.arow[xs])
+    edges.append(np.stack([w[keep], m.arow[xs][keep]], axis=1))
+    if missing:
+        row, mop, k, v = min(missing)
+        e = IllegalHistory("no-writer", row)
+        e.mop, e.key, e.value = mop, k, v
+        raise e
+    # rw: the counted reads of k of length i -> the append at position i
+    span = int(m.rlen[cr].max()) + 1 if len(cr) else 1
+    rsort = cr[np.argsort(m.rk[cr] * span + m.rlen[cr], kind="stable")]
+    rkeys = m.rk[rsort] * span + m.rlen[rsort]
+    xs = ca[pos >= 0]
+    q = m.ak[xs] * span + pos[pos >= 0]
+    lo_, hi_ = np.searchsorted(rkeys, q, side="left"), np.searchsorted(rkeys, q, side="right")
+    cnt = hi_ - lo_
+    dst = np.repeat(m.arow[xs], cnt)
+    within = np.arange(int(cnt.sum())) - np.repeat(np.cumsum(cnt) - cnt, cnt)
+    src = m.rrow[rsort[np.repeat(lo_, cnt) + within]]
+    edges.append(np.stack([src, dst], axis=1)[src != dst])
+    return np.concatenate(edges).astype(np.int64).reshape(-1, 2)
+
+
+def _mop_types_map(history):
+    bad = [op for op in history if not all(m[0] in READ_FS + (APPEND_F,) for m in (op.get("value") or ()))]
+    return {"valid?": "unknown", "type": "unexpected-txn-micro-op-types",
+            "message": "history contained operations other than appends or reads", "examples": bad[:8]} if bad else None
+
+
+def _duplicate_appends_map(op, mop):
+    _, k, v = op["value"][mop]
+    return {"valid?": "unknown", "type": "duplicate-appends", "op": op, "key": k, "value": v,
+            "message": f"value {pr_str(v)} appended to key {pr_str(k)} multiple times!"}
+
+
+def _duplicate_elements_map(op, mop):
+    _, k, v = op["value"][mop]
+    freq = {}
+    for x in v:
+        freq[x] = freq.get(x, 0) + 1
+    return {"valid?": False, "type": "duplicate-elements",
+            "message": "Observed multiple copies of a value which was only inserted once",
+            "op": op, "key": k, "value": v, "duplicates": {x: c for x, c in sorted(freq.items()) if c > 1}}
+
+
+def _is_prefix(a, b):
+    a, b = a or (), b or ()
+    return len(a) <= len(b) and all(x == y for x, y in zip(a, b))
+
+
+def total_order_map(history, bad_keys):
+    """The :no-total-state-order map over the keys `bad_keys`: per key its distinct
+    :ok / :info reads sorted by (length, first appearance) and their first
+    adjacent pair that is no prefix pair; keys in first-appearance order."""
+    seen = {}
+    for op in history:
+        if op.get("type") in ("ok", "info") and op.get("process") != "nemesis":
+            for f, k, v in (op.get("value") or ()):
+                if f in READ_FS and k in bad_keys:
+                    seen.setdefault(k, {}).setdefault(None if v is None else tuple(v), v)
+    errors = []
+    for k, by_value in seen.items():
+        vs = sorted(by_value.values(), key=lambda v: len(v or ()))
+        for a, b in zip(vs, vs[1:]):
+            if not _is_prefix(a, b):
+                errors.append({"key": k, "values": [a, b]})
+                break
+    return {"valid?": False, "type": "no-total-state-order",
+            "message": "observed mutually incompatible orders of appends", "errors": errors}
+
+
+def appends_and_reads_graph(history):
+    """cycle.clj:575-699. Raises AnalysisMap for a check that throws a map with
+    :valid? (check_host returns it) and IllegalHistory for a missing writer."""
+    history = list(history)
+    bad = _mop_types_map(history)
+    if bad:
+        raise AnalysisMap(bad)
+    try:
+        cols = encode_append(history)
+    except TypeError:
+        cols = encode_append(history, strict=False)
+    m = _Mops(cols)
+    at = duplicate_append(m)
+    if at:
+        raise AnalysisMap(_duplicate_appends_map(history[at[0]], at[1]))
+    at = duplicate_read(m)
+    if at:
+        raise AnalysisMap(_duplicate_elements_map(history[at[0]], at[1]))
+    bad_keys = bad_order_keys(m)
+    if bad_keys:
+        raise AnalysisMap(total_order_map(history, {cols.keys[k] for k in bad_keys}))
+    return Graph(len(history), append_edges(m)), AppendsAndReadsExplainer()
+
+
 # -- the checker --------------------------------------------------------------------
 def _result(graph, explainer, sccs, history):
     return {"valid?": not sccs, "scc-count": len(sccs),
@@ -506,6 +794,8 @@ def check_host(analyze_fn, history):
     history = [op for op in _indexed(history) if op.get("process") != "nemesis"]
     try:
         graph, explainer = analyze_fn(history)
+    except AnalysisMap as e:                  # the reference's try+: a map with :valid? is the result
+        return e.map
     except IllegalArgument as e:              # positions in the filtered history -> the ops' own :index
         e.row, e.rows = history[e.row]["index"], [history[j]["index"] for j in e.rows]
         raise
@@ -516,7 +806,7 @@ def check_host(analyze_fn, history):
 
 
 def _explainer_for(analyze_fn, history):
-    table = {process_graph: ProcessExplainer, wr_graph: WRExplainer}
+    table = {process_graph: ProcessExplainer, wr_graph: WRExplainer, appends_and_reads_graph: AppendsAndReadsExplainer}
     parts = getattr(analyze_fn, "parts", (analyze_fn,))
     out = []
     for p in parts:
@@ -541,6 +831,19 @@ def raise_unknown(res, history, keys):
     raise IllegalHistory(A.CAUSES[cause], row)
 
 
+def append_map(res, history, cols):
+    """The reference's map for causes 13-15, from the row the device names."""
+    op, at = history[res["unknown_row"]], res["unknown_rows"][0]
+    if res["cause"] == A.CAUSE_DUPLICATE_APPENDS:
+        return _duplicate_appends_map(op, at)
+    if res["cause"] == A.CAUSE_DUPLICATE_ELEMENTS:
+        return _duplicate_elements_map(op, at)
+    out = total_order_map(history, {cols.keys[k] for k in bad_order_keys(_Mops(cols))})
+    if len(out["errors"]) != at:
+        raise RuntimeError(f"cycle: the device names {at} keys without a total order, the host {len(out['errors'])}")
+    return out
+
+
 class CycleChecker:
     """(cycle/checker analyze-fn). path: 0 auto, 1 on-chip, 2 global tier.
     device=False keeps everything on the host."""
@@ -553,10 +856,10 @@ class CycleChecker:
         from . import checker as K
         mask = getattr(self.analyze_fn, "analyzers", None)
         history = _indexed(history)
-        if not self.device or not mask:
+        if not self.device or not mask or (mask & A.CY_APPEND and mask & A.CY_WR):
             return check_host(self.analyze_fn, history)
         try:
-            cols = encode(history, txns=bool(mask & A.CY_WR))
+            cols = encode_append(history) if mask & A.CY_APPEND else encode(history, txns=bool(mask & A.CY_WR))
         except (TypeError, ValueError):
             return check_host(self.analyze_fn, history)
         try:
@@ -568,6 +871,8 @@ class CycleChecker:
             if e.code != A.JH_EUNSUPPORTED:
                 raise
             return check_host(self.analyze_fn, history)
+        if res["cause"] in (A.CAUSE_DUPLICATE_APPENDS, A.CAUSE_DUPLICATE_ELEMENTS, A.CAUSE_NO_TOTAL_ORDER):
+            return append_map(res, history, cols)
         if res["valid"] == A.UNKNOWN:
             raise_unknown(res, history, cols.keys)
         sccs = res["sccs"]
@@ -583,3 +888,6 @@ class CycleChecker:
 
 def checker(analyze_fn, path=A.CY_PATH_AUTO, device=True):
     return CycleChecker(analyze_fn, path, device)
+
+
+appends_and_reads_graph.analyzers = A.CY_APPEND

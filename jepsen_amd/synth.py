@@ -866,3 +866,89 @@ def txn_cycle_columns_to_ops(cols):
         out.append({"process": p if p >= 0 else "nemesis", "type": ("invoke", "ok", "fail", "info")[int(cols.type[i])],
                     "f": "txn", "value": v})
     return out
+
+
+def append_history(n_txns=1000, procs=10, keys=100, anomalies=0, p_info=0.02, seed=0, max_len=64):
+    """A list-append history for appends-and-reads-graph as Columns (include/jh.h,
+    "Append txns"): n_txns txns of `procs` processes, each [:r k v] [:append k' x]
+    over `keys` live keys, under a serial schedule: a txn takes effect at its
+    invocation, so every dependency follows invocation order and the healthy
+    history has no cycle, with or without the realtime edges. A key's elements
+    are 1, 2, ... in append order, so a read of length c is [1 .. c]. A key whose
+    list reaches max_len is left for a fresh one, so read lengths stay below
+    max_len. Invocations carry the txn with a nil read; an :info completion
+    (its process is replaced) carries the append alone. anomalies: that many :ok
+    txns read a shorter prefix than the state they were given (a stale read: an
+    rw edge back to a txn that went before)."""
+    from . import _abi as A
+    rng = np.random.default_rng(seed)
+    live = list(range(keys))                     # slot -> key id
+    length = [0] * keys                          # key id -> elements so far
+    proc, typ, val, val2 = [], [], [], []
+    rk, rlen, ak, av = np.zeros(n_txns, np.int64), np.zeros(n_txns, np.int64), np.zeros(n_txns, np.int64), np.zeros(n_txns, np.int64)
+    open_, pid, started, at = {}, list(range(procs)), 0, 0
+    slots = rng.integers(procs, size=4 * n_txns + 4 * procs)
+    picks = rng.integers(keys, size=(n_txns, 2))
+    infos = rng.random(n_txns) < p_info
+    ok_txns = []
+    while started < n_txns or open_:
+        s = int(slots[at % len(slots)])
+        at += 1
+        if s in open_:
+            t = open_.pop(s)
+            proc.append(pid[s])
+            if infos[t]:
+                typ.append(A.TYPE_INFO); val.append(16 * t + 4); val2.append(1)
+                pid[s] += procs
+            else:
+                typ.append(A.TYPE_OK); val.append(16 * t + 8); val2.append(2)
+                ok_txns.append(t)
+        elif started < n_txns:
+            t = started
+            kr, kw = live[int(picks[t, 0])], live[int(picks[t, 1])]
+            rk[t], rlen[t] = kr, length[kr]
+            length[kw] += 1
+            ak[t], av[t] = kw, length[kw]
+            if length[kw] >= max_len:
+                live[int(picks[t, 1])] = len(length)
+                length.append(0)
+            open_[s] = t
+            proc.append(pid[s]); typ.append(A.TYPE_INVOKE); val.append(16 * t); val2.append(2)
+            started += 1
+    stale = [t for t in ok_txns if rlen[t] >= 2]
+    for t in (rng.choice(stale, size=min(anomalies, len(stale)), replace=False).tolist() if stale and anomalies else ()):
+        rlen[t] = int(rng.integers(0, rlen[t]))
+    # words: per txn [r k _ 0] [append k' x 0] (the invocation) and [r k off len] [append k' x 0] (the :ok completion)
+    words = np.zeros((n_txns, 16), np.int64)
+    off = 16 * n_txns + np.cumsum(rlen) - rlen
+    for base, ln_col in ((0, None), (8, rlen)):
+        words[:, base], words[:, base + 1] = A.F_READ, rk
+        words[:, base + 4], words[:, base + 5], words[:, base + 6] = A.F_APPEND, ak, av
+        if ln_col is not None:
+            words[:, base + 2], words[:, base + 3] = off, ln_col
+    total = int(rlen.sum())
+    elems = np.arange(total, dtype=np.int64) - np.repeat(np.cumsum(rlen) - rlen, rlen) + 1
+    n = len(proc)
+    return Columns(n=n, process=np.asarray(proc, np.int64), type=np.asarray(typ, np.int64),
+                   f=np.full(n, A.F_FIRST_INTERNED, np.int64), key=np.full(n, -1, np.int64), value=np.asarray(val, np.int64),
+                   value2=np.asarray(val2, np.int64), n_keys=len(length), aux=np.concatenate([words.reshape(-1), elems]),
+                   keys=list(range(len(length))), f_names=["txn"])
+
+
+def append_columns_to_ops(cols):
+    """Op maps of Columns in the append txn encoding (append_history's, or
+    cycle.encode_append's): every row carries its txn; an empty read is nil."""
+    from . import _abi as A
+    out = []
+    for i in range(cols.n):
+        v = None
+        if int(cols.value2[i]) > 0 or int(cols.value[i]) != A.NIL:
+            s, c = int(cols.value[i]), int(cols.value2[i])
+            v = []
+            for f, k, a, b in np.asarray(cols.aux[s:s + 4 * c]).reshape(-1, 4).tolist():
+                v.append(["r", cols.keys[k], cols.aux[a:a + b].tolist() if b else None] if f == A.F_READ
+                         else ["append", cols.keys[k], a])
+        p = int(cols.process[i])
+        out.append({"process": p if p >= 0 else "nemesis", "type": ("invoke", "ok", "fail", "info")[int(cols.type[i])],
+                    "f": "txn", "value": v})
+    return out
