@@ -930,8 +930,21 @@ int jh_check_causal_reverse(jh_ctx *ctx, const jh_history *h, const jh_causal_re
  *                  16 NO_WRITER          JH_UNKNOWN  row          micro-op index   k            the element nobody appended
  *                  unknown_rows[1] is -1 in all four. JH_INVALID with cause == 0
  *                  keeps meaning "SCCs".
- *  extra edges     opts->extra_src / extra_dst / n_extra: host int64 history rows
- *                  (monotonic-key edges are built by the shim).
+ *  JH_CY_MONOTONIC monotonic-key-graph, cycle.clj:218-267, over the :ok rows of
+ *                  any process, each row's :value a map {key value} encoded as
+ *                  "Map reads encoding" below; not together with JH_CY_WR or
+ *                  JH_CY_APPEND (JH_EINVAL: they read aux differently and share
+ *                  edge_count[2]). For every key separately the rows that hold
+ *                  it are grouped by their value of it and the groups ordered by
+ *                  value as signed int64 (JH_NIL = INT64_MIN comes first, where
+ *                  the reference's compare puts nil); every row of a group links
+ *                  to every row of the key's next group. Values need not be
+ *                  adjacent ({0, 1, 4}: 0 -> 1 and 1 -> 4); a key with a single
+ *                  group gives nothing; a row is in one group per key, so there
+ *                  are no self-loops; two rows linked through two keys count
+ *                  twice. Rows of other types are not read.
+ *  extra edges     opts->extra_src / extra_dst / n_extra: host int64 history rows,
+ *                  for edges of analyzers the caller builds itself.
  * With several causes the first of: double invoke, orphan, unmatched invoke,
  * multiple writes, then 13, 14, 15, 16 is reported; edges and SCCs are not
  * computed then (scc_count = 0, labels_out all -1).
@@ -946,6 +959,16 @@ int jh_check_causal_reverse(jh_ctx *ctx, const jh_history *h, const jh_causal_re
  * it edge_count[2] = the number of link calls of the reference (repeats are
  * counted, pairs of a row with itself are not) and entries = micro-ops scanned
  * plus read elements scanned.
+ *
+ * Map reads encoding (JH_CY_MONOTONIC only; the pair layout of the bank and
+ * long-fork reads): an :ok row has value = the index of its first pair and
+ * value2 = its number of pairs; pair j is aux[2*(value+j)] (the key, an int64
+ * the caller interned) and aux[2*(value+j)+1] (the value, an int64 or JH_NIL);
+ * n_aux is even. A nil or empty map is value2 = 0, and value is then not looked
+ * at. Ranges need not be contiguous or ordered in aux. With it edge_count[2] =
+ * the number of link calls (the sum over keys and successive groups of
+ * |A| * |B|) and entries = pairs scanned. The edge count is decided from 64-bit
+ * counts before any edge buffer is sized.
  *
  * SCCs. An edge with dst < src is a back edge; every cycle holds one, and the
  * row intervals [dst, src] of the back edges, merged where they overlap, are
@@ -974,7 +997,11 @@ int jh_check_causal_reverse(jh_ctx *ctx, const jh_history *h, const jh_causal_re
  * L_k) and is longer than JH_CY_AP_DIRECT_READ elements. JH_EINVAL with
  * JH_CY_APPEND: a micro-op or element range leaving [0, n_aux), a negative
  * count, a key outside [0, n_keys), an element equal to JH_NIL, JH_CY_APPEND |
- * JH_CY_WR. JH_EINVAL otherwise: a txn range leaving
+ * JH_CY_WR. With JH_CY_MONOTONIC: JH_EUNSUPPORTED for a row of more than
+ * JH_CY_MAX_MOPS pairs and for more than 2^31 - 2 records; JH_EINVAL for a pair
+ * range leaving [0, n_aux / 2), a negative count, an odd n_aux, a row that names
+ * one key twice, JH_CY_MONOTONIC | JH_CY_WR and JH_CY_MONOTONIC | JH_CY_APPEND.
+ * JH_EINVAL otherwise: a txn range leaving
  * [0, n_aux / 3), a negative count, n_aux % 3 != 0, an edge endpoint outside
  * [0, n), analyzers == 0 with no extra edges, a :type outside 0..3, path 1
  * forced with a region of more than JH_CY_LDS_VERTICES vertices. */
@@ -983,6 +1010,7 @@ int jh_check_causal_reverse(jh_ctx *ctx, const jh_history *h, const jh_causal_re
 #define JH_CY_REALTIME 2
 #define JH_CY_WR       4
 #define JH_CY_APPEND   16                /* (8 is not an analyzer) */
+#define JH_CY_MONOTONIC 32
 #define JH_F_APPEND    7                 /* micro-op f of an append txn */
 #define JH_CY_AP_DIRECT_READ 4096        /* elements of a read the direct duplicate check takes (a cap on a slow path) */
 #define JH_CAUSE_DUPLICATE_APPENDS  13   /* cycle, JH_CY_APPEND: see the table above */
@@ -990,7 +1018,7 @@ int jh_check_causal_reverse(jh_ctx *ctx, const jh_history *h, const jh_causal_re
 #define JH_CAUSE_NO_TOTAL_ORDER     15
 #define JH_CAUSE_NO_WRITER          16
 #define JH_CY_LDS_VERTICES 2048          /* vertices of a region of the on-chip tier (16 B each) */
-#define JH_CY_MAX_MOPS 64                /* micro-ops per txn */
+#define JH_CY_MAX_MOPS 64                /* micro-ops per txn; pairs per map (JH_CY_MONOTONIC) */
 #define JH_CY_WORK_MULT 64               /* work cap of a region: this * (vertices + edges) edge visits */
 
 typedef struct jh_cycle_opts {
@@ -1006,11 +1034,11 @@ typedef struct jh_cycle_result {
     int32_t path;                  /* 1: every region on chip, 2: some region in the global tier, 0: no region */
     int32_t pad;
     int64_t scc_count, scc_vertices;
-    int64_t edge_count[4];         /* process, realtime, wr or append, extra (jh_scc: all in [3]); self-loops and repeats counted */
+    int64_t edge_count[4];         /* process, realtime, wr / append / monotonic, extra (jh_scc: all in [3]); self-loops and repeats counted */
     int64_t back_edges;
     int64_t regions, max_region, global_regions;   /* regions of >= 2 vertices; the largest one's vertices */
     int64_t unknown_row, unknown_key, unknown_value, unknown_rows[2];   /* -1 / JH_NIL / JH_NIL / -1 when unused */
-    int64_t entries;               /* micro-ops scanned (JH_CY_APPEND: plus read elements scanned) */
+    int64_t entries;               /* micro-ops scanned (JH_CY_APPEND: plus read elements scanned; JH_CY_MONOTONIC: pairs scanned) */
     double device_ms;
 } jh_cycle_result;
 

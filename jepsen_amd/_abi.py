@@ -264,6 +264,7 @@ CAUSE_DOUBLE_INVOKE, CAUSE_ORPHAN, CAUSE_UNMATCHED_INVOKE = 3, 4, 12
 CAUSES[12] = "unmatched-invoke"
 # appends-and-reads-graph (additive to ABI 8)
 CY_APPEND = 16                # JH_CY_APPEND (8 is not an analyzer)
+CY_MONOTONIC = 32             # JH_CY_MONOTONIC: monotonic-key-graph over map reads
 F_APPEND = 7                  # JH_F_APPEND: micro-op f of an append txn
 CY_AP_DIRECT_READ = 4096      # JH_CY_AP_DIRECT_READ: elements of a read the direct duplicate check takes
 CAUSE_DUPLICATE_APPENDS, CAUSE_DUPLICATE_ELEMENTS, CAUSE_NO_TOTAL_ORDER, CAUSE_NO_WRITER = 13, 14, 15, 16

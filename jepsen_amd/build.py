@@ -17,7 +17,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
-HIP_SOURCES = ["jh_lin.hip", "jh_counter.hip", "jh_set.hip", "jh_setfull.hip", "jh_queue.hip", "jh_uids.hip", "jh_bank.hip", "jh_longfork.hip", "jh_causal.hip", "jh_cycle.hip", "jh_cycle_append.hip", "jh_api.hip", "jh_multi.hip", "jh_ingest.hip"]
+HIP_SOURCES = ["jh_lin.hip", "jh_counter.hip", "jh_set.hip", "jh_setfull.hip", "jh_queue.hip", "jh_uids.hip", "jh_bank.hip", "jh_longfork.hip", "jh_causal.hip", "jh_cycle.hip", "jh_cycle_append.hip", "jh_cycle_mono.hip", "jh_api.hip", "jh_multi.hip", "jh_ingest.hip"]
 HOST_SOURCES = ["jh_io.cpp"]
 HEADERS = [os.path.join(CSRC, "jh_internal.h"), os.path.join(CSRC, "cycle_common.h"), os.path.join(ROOT, "include", "jh.h")]
 # headers jh_lin.hip alone includes (csrc/lin/*.h): whatever the directory holds

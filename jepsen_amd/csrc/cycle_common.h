@@ -1,10 +1,12 @@
-// cycle_common.h -- what jh_cycle.hip and jh_cycle_append.hip share: the packed
+// cycle_common.h -- what jh_cycle.hip, jh_cycle_append.hip and jh_cycle_mono.hip share: the packed
 // edge word, the grid-stride loop, the (k, v) hash with its sorted-hash lookup,
-// and the hipcub wrappers over the WS_CY_TMP scratch. Everything is internal to
+// the hipcub wrappers over the WS_CY_TMP scratch, and the arena that lays a run
+// of device arrays out behind one workspace slot. Everything is internal to
 // the including file (anonymous namespace).
 #pragma once
 #include "jh_internal.h"
 #include <hipcub/hipcub.hpp>
+#include <algorithm>
 
 namespace {
 typedef unsigned long long u64;
@@ -69,5 +71,25 @@ void sort_pairs(jh_ctx *ctx, const u64 *kin, u64 *kout, const uint32_t *vin, uin
     size_t tb = 0;
     HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, kin, kout, vin, vout, (int)cnt, 0, 64, st));
     HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp(ctx, tb), tb, kin, kout, vin, vout, (int)cnt, 0, 64, st));
+}
+
+// a run of device arrays behind one workspace slot: laid out twice, to size and to place
+struct Arena {
+    char *p;
+    size_t off = 0;
+    template <class T>
+    void take(T *&out, long long cnt) {
+        off = (off + 15) & ~(size_t)15;
+        out = p ? (T *)(p + off) : nullptr;
+        off += sizeof(T) * (size_t)std::max<long long>(cnt, 1);
+    }
+};
+
+template <class F>
+void carve(jh_ctx *ctx, int slot, F layout) {
+    Arena size{nullptr};
+    layout(size);
+    Arena place{ctx->ws<char>(slot, size.off)};
+    layout(place);
 }
 }  // namespace

@@ -584,12 +584,16 @@ int jh_check_cycle(jh_ctx *ctx, const jh_history *h, const jh_cycle_opts *opts, 
     if (!ctx || !res || !opts) { set_err(err, errlen, "null argument"); return JH_EINVAL; }
     if (opts->path < 0 || opts->path > 2) { set_err(err, errlen, "path is 0, 1 or 2"); return JH_EINVAL; }
     if (opts->n_extra < 0) { set_err(err, errlen, "cycle: n_extra < 0"); return JH_EINVAL; }
-    if ((opts->analyzers & ~(JH_CY_PROCESS | JH_CY_REALTIME | JH_CY_WR | JH_CY_APPEND)) != 0) {
+    if ((opts->analyzers & ~(JH_CY_PROCESS | JH_CY_REALTIME | JH_CY_WR | JH_CY_APPEND | JH_CY_MONOTONIC)) != 0) {
         set_err(err, errlen, "cycle: an unknown analyzer bit");
         return JH_EINVAL;
     }
     if ((opts->analyzers & JH_CY_APPEND) && (opts->analyzers & JH_CY_WR)) {
         set_err(err, errlen, "cycle: JH_CY_APPEND and JH_CY_WR read the txn columns differently");
+        return JH_EINVAL;
+    }
+    if ((opts->analyzers & JH_CY_MONOTONIC) && (opts->analyzers & (JH_CY_WR | JH_CY_APPEND))) {
+        set_err(err, errlen, "cycle: JH_CY_MONOTONIC reads aux as (key, value) pairs, JH_CY_WR and JH_CY_APPEND as txns");
         return JH_EINVAL;
     }
     if (opts->analyzers == 0 && opts->n_extra == 0) {
@@ -606,8 +610,11 @@ int jh_check_cycle(jh_ctx *ctx, const jh_history *h, const jh_cycle_opts *opts, 
         const bool app = (opts->analyzers & JH_CY_APPEND) != 0;
         if (app && (h->n_aux < 0 || h->n_keys < 0)) throw_jh(JH_EINVAL, "cycle: n_aux and n_keys must be >= 0");
         if (app && h->n_aux > 0 && !h->aux) throw_jh(JH_EINVAL, "cycle: n_aux > 0 without aux");
+        const bool mono = (opts->analyzers & JH_CY_MONOTONIC) != 0;
+        if (mono && (h->n_aux < 0 || h->n_aux % 2 != 0)) throw_jh(JH_EINVAL, "cycle: n_aux must be even and >= 0");
+        if (mono && h->n_aux > 0 && !h->aux) throw_jh(JH_EINVAL, "cycle: n_aux > 0 without aux");
         HIP_TRY(hipSetDevice(ctx->device));
-        jh_history d = stage_history(ctx, h, false, wr || app);
+        jh_history d = stage_history(ctx, h, false, wr || app || mono);
         const CycleOut out = {labels_out, scc_off, scc_rows, scc_cap, rows_cap, edges_out, edge_cap};
         cycle_check(ctx, &d, opts, res, out, ctx->stream);
     });

@@ -20,8 +20,12 @@
 //                     appends-and-reads-graph (JH_CY_APPEND, in place of wr) is
 //                     jh_cycle_append.hip: append_plan verifies and sizes,
 //                     append_fill writes the wr / ww / rw slots.
+//                     monotonic-key-graph (JH_CY_MONOTONIC) is jh_cycle_mono.hip:
+//                     mono_plan sorts the (k, v, row) records and counts,
+//                     mono_fill writes every edge.
 //                     Builders leave holes (~0) where a slot has no edge; one
-//                     select compacts process | realtime | wr | append | extra.
+//                     select compacts process | realtime | wr | append |
+//                     monotonic | extra.
 //   2. regions        reach[dst] = max src over the back edges (atomicMax), an
 //                     inclusive max-scan, boundary flags and their prefix sum:
 //                     the regions of >= 2 vertices as [start, end] row intervals.
@@ -837,20 +841,25 @@ void cycle_check(jh_ctx *ctx, const jh_history *dh, const jh_cycle_opts *opts, j
         ap = append_plan(ctx, dh, res, st);
         if (ap.cause) { timer.stop(); return; }
     }
+    // monotonic-key: the sorted records and the number of its edges (jh_cycle_mono.hip)
+    MonoPlan mp;
+    if (an & JH_CY_MONOTONIC) mp = mono_plan(ctx, dh, res, st);
     long long R = 0, W = 0;
     if (an & JH_CY_WR) {
         HIP_TRY(hipMemcpyAsync(&R, ro + n, sizeof R, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipMemcpyAsync(&W, wo + n, sizeof W, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
     }
-    const long long n_raw = n_proc_slots + n_rt + R + ap.slots + (long long)extra.size();
+    const long long n_raw = n_proc_slots + n_rt + R + ap.slots + mp.slots + (long long)extra.size();
     if (n_rt > Y_MAX || R > Y_MAX || W > Y_MAX || n_raw > Y_MAX)
         throw_jh(JH_EUNSUPPORTED, "cycle: more than 2^31 - 2 vertices or edges");
 
-    // every builder's slots in one buffer: process | realtime | wr | append | extra
+    // every builder's slots in one buffer: process | realtime | wr | append | monotonic | extra
     u64 *raw = ctx->ws<u64>(WS_CY_RAW, n_raw);
-    u64 *raw_rt = raw + n_proc_slots, *raw_wr = raw_rt + n_rt, *raw_ap = raw_wr + R, *raw_x = raw_ap + ap.slots;
+    u64 *raw_rt = raw + n_proc_slots, *raw_wr = raw_rt + n_rt, *raw_ap = raw_wr + R, *raw_mo = raw_ap + ap.slots;
+    u64 *raw_x = raw_mo + mp.slots;
     const long long ap_links = (an & JH_CY_APPEND) ? append_fill(ctx, ap, raw_ap, st) : 0;
+    mono_fill(ctx, mp, raw_mo, st);
     if (n_proc_slots) HIP_TRY(hipMemcpyAsync(raw, proc_raw, sizeof(u64) * n, hipMemcpyDeviceToDevice, st));
     if (n_rt > 0) k_cy_rt_fill<<<grid_for(n_rt, 256, 4096), 256, 0, st>>>(rt_off, ip, icomp, n, n_rt, raw_rt);
     if (R > 0) {
@@ -878,7 +887,7 @@ void cycle_check(jh_ctx *ctx, const jh_history *dh, const jh_cycle_opts *opts, j
     }
     res->edge_count[0] = (int64_t)mh.edges[0];
     res->edge_count[1] = n_rt;
-    res->edge_count[2] = (an & JH_CY_APPEND) ? ap_links : (int64_t)mh.edges[2];
+    res->edge_count[2] = (an & JH_CY_APPEND) ? ap_links : (an & JH_CY_MONOTONIC) ? mp.slots : (int64_t)mh.edges[2];
     u64 *edges = ctx->ws<u64>(WS_CY_EDGES, n_raw);
     const long long E = select_edges(ctx, raw, edges, n_raw, st);
     scc_core(ctx, n, edges, E, opts->path, res, out, m, st);

@@ -409,26 +409,6 @@ __global__ void __launch_bounds__(256) k_ap_report(const AP a, int cause) {
     if (threadIdx.x == 0) { a.m->key = k; a.m->value = value; }
 }
 
-// a run of device arrays behind one workspace slot: laid out twice, to size and to place
-struct Arena {
-    char *p;
-    size_t off = 0;
-    template <class T>
-    void take(T *&out, long long cnt) {
-        off = (off + 15) & ~(size_t)15;
-        out = p ? (T *)(p + off) : nullptr;
-        off += sizeof(T) * (size_t)std::max<long long>(cnt, 1);
-    }
-};
-
-template <class F>
-void carve(jh_ctx *ctx, int slot, F layout) {
-    Arena size{nullptr};
-    layout(size);
-    Arena place{ctx->ws<char>(slot, size.off)};
-    layout(place);
-}
-
 void finish(jh_cycle_result *res, int valid, int cause, long long row, long long r0, long long key, long long value) {
     res->valid = valid; res->cause = cause; res->unknown_row = row;
     res->unknown_rows[0] = r0; res->unknown_rows[1] = -1;

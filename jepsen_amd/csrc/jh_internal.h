@@ -134,6 +134,7 @@ enum WsSlot {
     WS_CY_TXN, WS_CY_REC, WS_CY_HASH, WS_CY_HIDX, WS_CY_RAW, WS_CY_EDGES, WS_CY_REACH, WS_CY_BS, WS_CY_REG, WS_CY_SEL,
     WS_CY_FWD, WS_CY_BWD, WS_CY_CSR, WS_CY_STATE, WS_CY_LABEL, WS_CY_SIZE, WS_CY_KEYS, WS_CY_VALS,
     WS_CY_AP_META, WS_CY_AP_ROWS, WS_CY_AP_RECS, WS_CY_AP_LONGEST,
+    WS_CY_MO_META, WS_CY_MO_ROWS, WS_CY_MO_RECS,
     WS_COUNT
 };
 
@@ -237,3 +238,13 @@ struct AppendPlan {
 };
 AppendPlan append_plan(jh_ctx *ctx, const jh_history *dh, jh_cycle_result *res, hipStream_t stream);
 long long append_fill(jh_ctx *ctx, const AppendPlan &plan, unsigned long long *raw, hipStream_t stream);
+// monotonic-key-graph (jh_cycle_mono.hip). mono_plan validates, sorts the (k, v, row) records and places the
+// edges (slots = their number, every one a real edge, decided from 64-bit counts; res->entries = the pairs
+// scanned); mono_fill writes plan.slots packed words
+struct MonoPlan {
+    long long records = 0, slots = 0;
+    const long long *eoff = nullptr;          // the builder's device arrays between the two calls
+    const int32_t *dstart = nullptr, *srow = nullptr;
+};
+MonoPlan mono_plan(jh_ctx *ctx, const jh_history *dh, jh_cycle_result *res, hipStream_t stream);
+void mono_fill(jh_ctx *ctx, const MonoPlan &plan, unsigned long long *raw, hipStream_t stream);

@@ -10,12 +10,13 @@ every SCC of more than one op as an anomaly:
 
 Vertices are positions in the history the analyzer was given (the checker gives
 every op an "index" first, so they are history rows). The module's own analyzers
-(process_graph, realtime_graph, wr_graph, appends_and_reads_graph and their
-`combine`) carry a mask of JH_CY_* bits: a checker over them makes ONE
-jh_check_cycle call when the values encode (include/jh.h, "Cycle txns" and
-"Append txns": keys are interned, values and list elements must be longs) and
-runs the host implementation otherwise (also for wr_graph combined with
-appends_and_reads_graph, which the device refuses). The host implementation is the
+(process_graph, realtime_graph, wr_graph, appends_and_reads_graph,
+monotonic_key_graph and their `combine`) carry a mask of JH_CY_* bits: a checker
+over them makes ONE jh_check_cycle call when the values encode (include/jh.h,
+"Cycle txns", "Append txns" and "Map reads encoding": keys are interned, values
+and list elements must be longs) and runs the host implementation otherwise
+(also for two of wr_graph, appends_and_reads_graph and monotonic_key_graph
+combined, which the device refuses). The host implementation is the
 numpy closed forms below; tests/cycle_ref.py holds the literal transcriptions
 they are tested against. Explanations run on the host over the at most 8
 reported SCCs.
@@ -363,6 +364,19 @@ class WRExplainer:
 class AppendsAndReadsExplainer:
     def explain_pair(self, a, b):
         return "something something"
+
+
+class MonotonicKeyExplainer:
+    """cycle.clj:220-236: the first key of a's map, in a's own key order, that b
+    holds too with both values non-nil and a's below b's."""
+
+    def explain_pair(self, a, b):
+        a, b = a.get("value") or {}, b.get("value") or {}
+        for k in a:
+            x, y = a[k], b.get(k)
+            if x is not None and y is not None and x < y:
+                return f"which observed {pr_str(k)} = {pr_str(x)}, and a higher value {pr_str(y)} was observed by"
+        return None
 
 
 class CombinedExplainer:
@@ -783,6 +797,115 @@ def appends_and_reads_graph(history):
     return Graph(len(history), append_edges(m)), AppendsAndReadsExplainer()
 
 
+# -- monotonic-key-graph (cycle.clj:218-267) -------------------------------------------
+def _map_records(history):
+    """(key id, value, row) of every pair of the :ok non-nemesis rows' maps, in row
+    order; keys interned in first-appearance order. TypeError for an :ok :value
+    that is neither a map nor nil."""
+    kid, val, row, key_ids = [], [], [], {}
+    for i, op in enumerate(history):
+        v = op.get("value")
+        if op.get("type") != "ok" or op.get("process") == "nemesis" or v is None:
+            continue
+        if not isinstance(v, dict):
+            raise TypeError(f"cycle: a map of {v!r}")
+        for k, x in v.items():
+            kid.append(key_ids.setdefault(k, len(key_ids)))
+            val.append(x)
+            row.append(i)
+    return np.asarray(kid, np.int64), val, np.asarray(row, np.int64), key_ids
+
+
+def _value_ranks(kid, val):
+    """Per record the rank of its value among its key's distinct values in
+    Python's own order, nil first (values that are no longs; TypeError for a
+    key whose values do not compare)."""
+    by_key = {}
+    for k, x in zip(kid.tolist(), val):
+        if x is not None:
+            by_key.setdefault(k, set()).add(x)
+    rank = {k: {x: i + 1 for i, x in enumerate(sorted(xs))} for k, xs in by_key.items()}
+    return np.asarray([0 if x is None else rank[k][x] for k, x in zip(kid.tolist(), val)], np.int64)
+
+
+def link_groups(kid, v, row):
+    """The closed form over records (key, value, row) as int64 arrays: sorted by
+    (k, v, row), every record links to every record of the next (k, v) group of
+    its key. One edge per link call. MemoryError, before anything of that size
+    is allocated, for more than 2^31 - 2 link calls."""
+    if len(kid) == 0:
+        return np.zeros((0, 2), np.int64)
+    o = np.lexsort((row, v, kid))
+    k_s, v_s, r_s = kid[o], v[o], row[o]
+    start = np.ones(len(o), bool)
+    start[1:] = (k_s[1:] != k_s[:-1]) | (v_s[1:] != v_s[:-1])
+    gid = np.cumsum(start) - 1
+    gstart = np.nonzero(start)[0]
+    gsize = np.diff(np.append(gstart, len(o)))
+    # per group: the start and size of the next group when it is of the same key
+    nsize = np.zeros(len(gstart), np.int64)
+    nstart = np.zeros(len(gstart), np.int64)
+    same = k_s[gstart[1:]] == k_s[gstart[:-1]]
+    nsize[:-1][same], nstart[:-1][same] = gsize[1:][same], gstart[1:][same]
+    cnt = nsize[gid]
+    total = int(cnt.sum(dtype=np.int64))
+    if total > (1 << 31) - 2:
+        raise MemoryError(f"cycle: monotonic-key-graph of {total} link calls (more than 2^31 - 2)")
+    if total == 0:
+        return np.zeros((0, 2), np.int64)
+    within = np.arange(total) - np.repeat(np.cumsum(cnt) - cnt, cnt)
+    return np.stack([np.repeat(r_s, cnt), r_s[np.repeat(nstart[gid], cnt) + within]], axis=1)
+
+
+def monotonic_key_edges(history):
+    """cycle.clj:238-267 over positions (link_groups over the maps' records). A
+    pair of rows linked through two keys stands twice. Values that are no longs
+    are ordered with Python's own comparison, nil first."""
+    kid, val, row, _ = _map_records(history)
+    try:
+        v = np.asarray([_long(x) for x in val], np.int64)
+    except TypeError:
+        v = _value_ranks(kid, val)
+    return link_groups(kid, v, row)
+
+
+def map_edges(cols):
+    """link_groups over Columns in the map reads encoding (what the device builds from them)."""
+    proc, typ, val2 = np.asarray(cols.process), np.asarray(cols.type), np.asarray(cols.value2)
+    rows = np.nonzero((typ == A.TYPE_OK) & (proc != -1) & (val2 > 0))[0]
+    cnt = val2[rows]
+    row = np.repeat(rows, cnt)
+    at = 2 * (np.repeat(np.asarray(cols.value)[rows], cnt) + np.arange(int(cnt.sum())) - np.repeat(np.cumsum(cnt) - cnt, cnt))
+    aux = np.asarray(cols.aux, np.int64)
+    return link_groups(aux[at], aux[at + 1], row) if len(row) else np.zeros((0, 2), np.int64)
+
+
+def monotonic_key_graph(history):
+    history = list(history)
+    return Graph(len(history), monotonic_key_edges(history)), MonotonicKeyExplainer()
+
+
+monotonic_key_graph.analyzers = A.CY_MONOTONIC
+
+
+def encode_map(history):
+    """Op maps -> Columns (include/jh.h, "Map reads encoding"): an :ok row's map
+    as (key, value) pairs in aux, keys interned in first-appearance order, nil ->
+    JH_NIL. TypeError for an :ok :value that is neither a map nor nil and for a
+    value that is no long."""
+    history = list(history)
+    n = len(history)
+    proc, typ = _encode_rows(history)
+    kid, vals, row, key_ids = _map_records(history)
+    val, val2 = np.full(n, A.NIL, np.int64), np.zeros(n, np.int64)
+    aux = np.zeros(2 * len(kid) + 2, np.int64)[:2 * len(kid)]
+    aux[0::2], aux[1::2] = kid, [_long(x) for x in vals]
+    rows, first, cnt = np.unique(row, return_index=True, return_counts=True)
+    val[rows], val2[rows] = first, cnt
+    return H.Columns(n=n, process=proc, type=typ, f=np.full(n, A.F_FIRST_INTERNED, np.int64), key=None, value=val,
+                     value2=val2, n_keys=0, aux=aux, keys=list(key_ids))
+
+
 # -- the checker --------------------------------------------------------------------
 def _result(graph, explainer, sccs, history):
     return {"valid?": not sccs, "scc-count": len(sccs),
@@ -806,7 +929,8 @@ def check_host(analyze_fn, history):
 
 
 def _explainer_for(analyze_fn, history):
-    table = {process_graph: ProcessExplainer, wr_graph: WRExplainer, appends_and_reads_graph: AppendsAndReadsExplainer}
+    table = {process_graph: ProcessExplainer, wr_graph: WRExplainer, appends_and_reads_graph: AppendsAndReadsExplainer,
+             monotonic_key_graph: MonotonicKeyExplainer}
     parts = getattr(analyze_fn, "parts", (analyze_fn,))
     out = []
     for p in parts:
@@ -856,10 +980,12 @@ class CycleChecker:
         from . import checker as K
         mask = getattr(self.analyze_fn, "analyzers", None)
         history = _indexed(history)
-        if not self.device or not mask or (mask & A.CY_APPEND and mask & A.CY_WR):
+        readers = [bit for bit in (A.CY_WR, A.CY_APPEND, A.CY_MONOTONIC) if mask and mask & bit]
+        if not self.device or not mask or len(readers) > 1:       # (each of them reads aux in its own way)
             return check_host(self.analyze_fn, history)
         try:
-            cols = encode_append(history) if mask & A.CY_APPEND else encode(history, txns=bool(mask & A.CY_WR))
+            cols = encode_append(history) if mask & A.CY_APPEND else encode_map(history) if mask & A.CY_MONOTONIC else \
+                encode(history, txns=bool(mask & A.CY_WR))
         except (TypeError, ValueError):
             return check_host(self.analyze_fn, history)
         try:

@@ -952,3 +952,78 @@ def append_columns_to_ops(cols):
         out.append({"process": p if p >= 0 else "nemesis", "type": ("invoke", "ok", "fail", "info")[int(cols.type[i])],
                     "f": "txn", "value": v})
     return out
+
+
+def monotonic_history(n_ops=1000, procs=10, keys=8, p_read=0.5, stale=0.0, p_info=0.02, seed=0):
+    """A history of the increment workload (tidb/src/tidb/monotonic.clj) for
+    monotonic-key-graph as Columns (include/jh.h, "Map reads encoding"): n_ops
+    ops of `procs` processes over `keys` counters that start at 0. An :inc of k
+    returns {k new}; a :read returns the current value of a random non-empty
+    subset of the keys. An op takes effect at its invocation, so the healthy
+    history has no cycle, alone or with the realtime and process edges. Every
+    invoke is completed; an :info completion (its process is replaced) carries
+    no map. stale: with that probability a :read returns one of its keys one
+    behind. p_read = 0 gives chains of unique values (groups of one row),
+    p_read near 1 a few values observed by many rows each (wide groups)."""
+    from . import _abi as A
+    rng = np.random.default_rng(seed)
+    cur = [0] * keys
+    proc, typ, f, val, val2, aux = [], [], [], [], [], []
+    open_, pid, started, at = {}, list(range(procs)), 0, 0
+    slots = rng.integers(procs, size=4 * n_ops + 4 * procs)
+    reads = rng.random(n_ops) < p_read
+    infos = rng.random(n_ops) < p_info
+    stales = rng.random(n_ops) < stale
+    inc_key = rng.integers(keys, size=n_ops)
+    held = rng.random((n_ops, keys)) < 0.5
+    while started < n_ops or open_:
+        s = int(slots[at % len(slots)])
+        at += 1
+        if s in open_:
+            t, pairs = open_.pop(s)
+            proc.append(pid[s]); f.append(A.F_FIRST_INTERNED + int(reads[t]))
+            if infos[t]:
+                typ.append(A.TYPE_INFO); val.append(A.NIL); val2.append(0)
+                pid[s] += procs
+            else:
+                typ.append(A.TYPE_OK); val.append(len(aux) // 2); val2.append(len(pairs) // 2)
+                aux += pairs
+        elif started < n_ops:
+            t = started
+            if reads[t]:
+                ks = np.nonzero(held[t])[0].tolist() or [int(inc_key[t])]
+                pairs = [x for k in ks for x in (k, cur[k])]
+                behind = [j for j in range(len(ks)) if pairs[2 * j + 1] > 0]
+                if stales[t] and behind:
+                    pairs[2 * behind[int(rng.integers(len(behind)))] + 1] -= 1
+            else:
+                k = int(inc_key[t])
+                cur[k] += 1
+                pairs = [k, cur[k]]
+            open_[s] = (t, pairs)
+            proc.append(pid[s]); typ.append(A.TYPE_INVOKE); f.append(A.F_FIRST_INTERNED + int(reads[t]))
+            val.append(A.NIL); val2.append(0)
+            started += 1
+    n = len(proc)
+    return Columns(n=n, process=np.asarray(proc, np.int64), type=np.asarray(typ, np.int64), f=np.asarray(f, np.int64),
+                   key=np.full(n, -1, np.int64), value=np.asarray(val, np.int64), value2=np.asarray(val2, np.int64), n_keys=0,
+                   aux=np.asarray(aux + [0, 0], np.int64)[:len(aux)], keys=list(range(keys)), f_names=["inc", "read"])
+
+
+def monotonic_columns_to_ops(cols):
+    """Op maps of Columns in the map reads encoding (monotonic_history's, or
+    cycle.encode_map's): an :ok row carries its map, every other row nil."""
+    from . import _abi as A
+    names = getattr(cols, "f_names", None) or ["read"]
+    out = []
+    for i in range(cols.n):
+        v = None
+        if int(cols.type[i]) == A.TYPE_OK and int(cols.value2[i]) > 0:
+            s, c = int(cols.value[i]), int(cols.value2[i])
+            v = {cols.keys[int(cols.aux[2 * j])]: (None if int(cols.aux[2 * j + 1]) == A.NIL else int(cols.aux[2 * j + 1]))
+                 for j in range(s, s + c)}
+        p = int(cols.process[i])
+        fi = int(cols.f[i]) - A.F_FIRST_INTERNED
+        out.append({"process": p if p >= 0 else "nemesis", "type": ("invoke", "ok", "fail", "info")[int(cols.type[i])],
+                    "f": names[fi] if 0 <= fi < len(names) else "read", "value": v})
+    return out
