@@ -241,6 +241,7 @@ class JhLongForkResult(C.Structure):
 
 CR_PATH_AUTO, CR_PATH_LDS, CR_PATH_GLOBAL = 0, 1, 2
 CR_LDS_VALUES = 1024          # JH_CR_LDS_VALUES: distinct values per key of the on-chip tier
+CR_TILE = 2048                # rows per tile of jh_causal.hip's scan (the tests straddle its edges)
 
 
 class JhCausalReverseOpts(C.Structure):

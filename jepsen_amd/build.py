@@ -19,7 +19,8 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 HIP_SOURCES = ["jh_lin.hip", "jh_counter.hip", "jh_set.hip", "jh_setfull.hip", "jh_queue.hip", "jh_uids.hip", "jh_bank.hip", "jh_longfork.hip", "jh_causal.hip", "jh_cycle.hip", "jh_cycle_append.hip", "jh_cycle_mono.hip", "jh_api.hip", "jh_multi.hip", "jh_ingest.hip"]
 HOST_SOURCES = ["jh_io.cpp"]
-HEADERS = [os.path.join(CSRC, "jh_internal.h"), os.path.join(CSRC, "cycle_common.h"), os.path.join(ROOT, "include", "jh.h")]
+# every header directly under csrc/ (a new one cannot be forgotten), and the public one
+HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(ROOT, "include", "jh.h")]
 # headers jh_lin.hip alone includes (csrc/lin/*.h): whatever the directory holds
 LIN_HEADERS = sorted(glob.glob(os.path.join(CSRC, "lin", "*.h")))
 HOST_HEADERS = [os.path.join(ROOT, "include", "jh.h"), os.path.join(ROOT, "include", "jh_io.h")]

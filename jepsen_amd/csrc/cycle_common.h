@@ -1,16 +1,14 @@
 // cycle_common.h -- what jh_cycle.hip, jh_cycle_append.hip and jh_cycle_mono.hip share: the packed
 // edge word, the grid-stride loop, the (k, v) hash with its sorted-hash lookup,
-// the hipcub wrappers over the WS_CY_TMP scratch, and the arena that lays a run
-// of device arrays out behind one workspace slot. Everything is internal to
-// the including file (anonymous namespace).
+// and the arena that lays a run of device arrays out behind one workspace slot.
+// The hipcub calls (over the WS_CY_TMP scratch), fetch and the op-type constants
+// come from jh_prims.h. Everything is internal to the including file (anonymous
+// namespace).
 #pragma once
-#include "jh_internal.h"
-#include <hipcub/hipcub.hpp>
-#include <algorithm>
+#include "jh_prims.h"
 
 namespace {
 typedef unsigned long long u64;
-constexpr int T_INVOKE = JH_TYPE_INVOKE, T_OK = JH_TYPE_OK, T_FAIL = JH_TYPE_FAIL, T_INFO = JH_TYPE_INFO;
 constexpr u64 HOLE = ~0ULL, NONE = ~0ULL;
 constexpr long long Y_MAX = 0x7ffffffeLL;
 
@@ -41,36 +39,6 @@ __device__ __forceinline__ long long cy_owner(const long long *__restrict__ off,
         else hi = mid - 1;
     }
     return lo;
-}
-
-char *tmp(jh_ctx *ctx, size_t bytes) { return ctx->ws<char>(WS_CY_TMP, bytes); }
-
-template <class T>
-T fetch(const T *dev, hipStream_t st) {
-    T h;
-    HIP_TRY(hipMemcpyAsync(&h, dev, sizeof h, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return h;
-}
-
-template <class T>
-void excl_sum(jh_ctx *ctx, const T *in, T *out, int64_t cnt, hipStream_t st) {
-    size_t tb = 0;
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, in, out, (int)cnt, st));
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp(ctx, tb), tb, in, out, (int)cnt, st));
-}
-
-void sort_keys(jh_ctx *ctx, const u64 *in, u64 *out, long long cnt, int end_bit, hipStream_t st) {
-    size_t tb = 0;
-    HIP_TRY(hipcub::DeviceRadixSort::SortKeys(nullptr, tb, in, out, (int)cnt, 0, end_bit, st));
-    HIP_TRY(hipcub::DeviceRadixSort::SortKeys(tmp(ctx, tb), tb, in, out, (int)cnt, 0, end_bit, st));
-}
-
-// stable: equal keys keep the order of their values' positions
-void sort_pairs(jh_ctx *ctx, const u64 *kin, u64 *kout, const uint32_t *vin, uint32_t *vout, long long cnt, hipStream_t st) {
-    size_t tb = 0;
-    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, kin, kout, vin, vout, (int)cnt, 0, 64, st));
-    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp(ctx, tb), tb, kin, kout, vin, vout, (int)cnt, 0, 64, st));
 }
 
 // a run of device arrays behind one workspace slot: laid out twice, to size and to place

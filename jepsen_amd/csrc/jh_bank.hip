@@ -7,7 +7,7 @@
 // wrong-total the lowest and highest total). A read's map is a CSR range of
 // (account code, balance) pairs in aux (include/jh.h).
 //
-// Pipeline:
+// Pipeline (stage 1's loops and host side are row_select.h):
 //   1. k_bank_flag     type / f in 16-byte row-pair loads: the :ok :read rows as
 //                      ballot words (one bit per row) and their number per
 //                      4096-row tile; an exclusive scan of the tile counts
@@ -42,15 +42,9 @@
 //                      total; block partials, one finishing block
 // No global atomic per read or per wave anywhere; the only atomics are the
 // error flags of a malformed range.
-#include "jh_internal.h"
-#include <hipcub/hipcub.hpp>
-#include <algorithm>
+#include "row_select.h"
 
 namespace {
-constexpr int T_OK = 1;
-constexpr int B_PAIRS = 8;                   // row pairs per thread per tile
-constexpr int B_TILE = 256 * B_PAIRS;        // row pairs per tile (4096 rows)
-constexpr int B_WORDS = B_PAIRS * 4 * 2;     // ballot words per tile (64)
 constexpr int B_STEPS = 16;
 constexpr int64_t B_SPAN = 64 * B_STEPS;     // entries per wave
 constexpr int C_RESUM = -1;                  // record class: to be re-summed in order
@@ -78,11 +72,6 @@ struct BPart {                // a piece of a read cut by a span edge
     long long r;              // -1: none
     BSum s;
 };
-
-__device__ __forceinline__ longlong2 b_ld_pair(const int64_t *__restrict__ c, int64_t i, int64_t n, bool vec) {
-    if (2 * i + 1 < n) return vec ? ((const longlong2 *)c)[i] : make_longlong2(c[2 * i], c[2 * i + 1]);
-    return make_longlong2(c[2 * i], 0);
-}
 
 // check-op's cond for a read whose sum is `total`
 __device__ __forceinline__ void b_classify(long long total, unsigned long long n_un, unsigned long long n_nil,
@@ -117,88 +106,33 @@ __device__ __forceinline__ void b_finish(const BSum &s, long long r, long long w
 }
 
 // ---------------------------------------------------------------------------
-// 1. the :ok :read rows. Tile = 256 threads x B_PAIRS row pairs, pair
-// p0 + u * 256 + thread; word ((tile * B_PAIRS + u) * 4 + wave) * 2 + h holds
-// the ballot of row 2p + h over the wave's 64 pairs.
+// 1. the :ok :read rows (row_select.h, pair layout, one kind)
 __global__ void __launch_bounds__(256) k_bank_flag(const int64_t *__restrict__ type, const int64_t *__restrict__ f,
                                                    int64_t n, int vec, unsigned long long *__restrict__ words,
                                                    long long *__restrict__ tile_cnt) {
-    __shared__ unsigned sh[4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t np = (n + 1) / 2, n_tiles = (np + B_TILE - 1) / B_TILE;
-    for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const int64_t p0 = tile * B_TILE + threadIdx.x;
-        longlong2 t2[B_PAIRS], f2[B_PAIRS];
-#pragma unroll
-        for (int u = 0; u < B_PAIRS; u++) {
-            const int64_t p = p0 + u * 256;
-            if (p < np) { t2[u] = b_ld_pair(type, p, n, vec); f2[u] = b_ld_pair(f, p, n, vec); }
-            else { t2[u] = make_longlong2(-1, -1); f2[u] = t2[u]; }
-        }
-        unsigned c = 0;
-#pragma unroll
-        for (int u = 0; u < B_PAIRS; u++) {
-            const int64_t p = p0 + u * 256;
-            const bool r0 = p < np && t2[u].x == T_OK && f2[u].x == JH_F_READ;
-            const bool r1 = 2 * p + 1 < n && t2[u].y == T_OK && f2[u].y == JH_F_READ;
-            const unsigned long long b0 = __ballot(r0), b1 = __ballot(r1);
-            c += __popcll(b0) + __popcll(b1);
-            if (lane < 2) words[((tile * B_PAIRS + u) * 4 + wave) * 2 + lane] = lane ? b1 : b0;
-        }
-        if (lane == 0) sh[wave] = c;
-        __syncthreads();
-        if (threadIdx.x == 0) tile_cnt[tile] = (long long)(sh[0] + sh[1] + sh[2] + sh[3]);
-        __syncthreads();
-    }
+    rs_flag_pairs<1>(type, f, n, vec, words, tile_cnt,
+                     [](int, const long long &t, const long long &ff) { return t == T_OK && ff == JH_F_READ; });
 }
 
-// (row, first pair, count) of every read, in history order. Every wave scans
-// the tile's 64 ballot words itself: the exclusive prefix of their popcounts
-// at word 2 * (u * 4 + wave) is where the wave's rows of step u go.
+// (row, first pair, count) of every read, in history order
 __global__ void __launch_bounds__(256) k_bank_compact(const int64_t *__restrict__ value, const int64_t *__restrict__ value2,
                                                       int64_t n, int vec, const unsigned long long *__restrict__ words,
                                                       const long long *__restrict__ tile_base, int64_t half,
                                                       int64_t *__restrict__ row, int64_t *__restrict__ start,
                                                       int64_t *__restrict__ cnt, BMeta *m) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const unsigned long long lt = (1ULL << lane) - 1;
-    const int64_t np = (n + 1) / 2, n_tiles = (np + B_TILE - 1) / B_TILE;
-    for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const unsigned long long w = words[tile * B_WORDS + lane];
-        unsigned inc = __popcll(w);
-        const unsigned own = inc;
+    rs_compact_pairs(n, words, tile_base, [&](int64_t p, bool r0, bool r1, long long o) {
+        const longlong2 v2 = ld_pair(value, p, n, vec), c2 = ld_pair(value2, p, n, vec);
 #pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const unsigned o = __shfl_up(inc, d);
-            if (lane >= d) inc += o;
+        for (int h = 0; h < 2; h++) {
+            if (!(h ? r1 : r0)) continue;
+            long long v = h ? v2.y : v2.x, c = h ? c2.y : c2.x;
+            if (v == JH_NIL) { v = 0; c = 0; }            // a nil :value is the empty map
+            else if (v < 0 || c < 0 || v > half || c > half - v) { atomicOr(&m->bad_range, 1u); v = 0; c = 0; }
+            else if (c > B_MAX_COUNT) { atomicOr(&m->too_long, 1u); v = 0; c = 0; }
+            row[o] = 2 * p + h; start[o] = v; cnt[o] = c;
+            o++;
         }
-        const unsigned excl = inc - own;
-        if (__shfl(inc, 63) == 0) continue;                   // no read in this tile
-        const long long base = tile_base[tile];
-        const int64_t p0 = tile * B_TILE + threadIdx.x;
-#pragma unroll
-        for (int u = 0; u < B_PAIRS; u++) {
-            const int wi = 2 * (u * 4 + wave);
-            const unsigned long long b0 = __shfl(w, wi), b1 = __shfl(w, wi + 1);
-            const unsigned at = __shfl(excl, wi);
-            if ((b0 | b1) == 0) continue;                     // wave-uniform
-            const int64_t p = p0 + u * 256;
-            const bool r0 = (b0 >> lane) & 1, r1 = (b1 >> lane) & 1;
-            if (!(r0 || r1)) continue;                        // nothing below is cross-lane
-            const longlong2 v2 = b_ld_pair(value, p, n, vec), c2 = b_ld_pair(value2, p, n, vec);
-            long long o = base + at + __popcll(b0 & lt) + __popcll(b1 & lt);
-#pragma unroll
-            for (int h = 0; h < 2; h++) {
-                if (!(h ? r1 : r0)) continue;
-                long long v = h ? v2.y : v2.x, c = h ? c2.y : c2.x;
-                if (v == JH_NIL) { v = 0; c = 0; }            // a nil :value is the empty map
-                else if (v < 0 || c < 0 || v > half || c > half - v) { atomicOr(&m->bad_range, 1u); v = 0; c = 0; }
-                else if (c > B_MAX_COUNT) { atomicOr(&m->too_long, 1u); v = 0; c = 0; }
-                row[o] = 2 * p + h; start[o] = v; cnt[o] = c;
-                o++;
-            }
-        }
-    }
+    });
 }
 
 // ---------------------------------------------------------------------------
@@ -541,13 +475,6 @@ __global__ void __launch_bounds__(256) k_bank_triples(const int64_t *__restrict_
     }
 }
 
-template <class T>
-void excl_scan(jh_ctx *ctx, const T *in, T *out, int64_t cnt, hipStream_t st) {
-    size_t tb = 0;
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, in, out, (int)cnt, st));
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(ctx->ws<char>(WS_B_TMP, tb), tb, in, out, (int)cnt, st));
-}
-
 }  // namespace
 
 void bank_check(jh_ctx *ctx, const jh_history *dh, const jh_bank_opts *opts, jh_bank_result *res,
@@ -561,36 +488,25 @@ void bank_check(jh_ctx *ctx, const jh_history *dh, const jh_bank_opts *opts, jh_
     if (dh->n_aux < 0 || (dh->n_aux & 1)) throw_jh(JH_EINVAL, "bank: n_aux must be even and >= 0 (pairs)");
     if (n == 0) return;
     if (n > 0x7fffffff00LL) throw_jh(JH_EUNSUPPORTED, "bank: more than 2^39 rows");
-    HIP_TRY(hipEventRecord(ctx->ev[0], st));
-    auto elapsed = [&] {
-        HIP_TRY(hipEventRecord(ctx->ev[1], st));
-        HIP_TRY(hipEventSynchronize(ctx->ev[1]));
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
-        res->device_ms = ms;
-    };
+    DeviceTimer timer{ctx, st};
+    timer.start();
     const long long want = opts->total_amount;
     const int negb = opts->negative_balances != 0;
     const int64_t half = dh->n_aux / 2;
 
     // 1. the reads, in history order
-    const int64_t np = (n + 1) / 2, n_tiles = (np + B_TILE - 1) / B_TILE;
     BMeta *m = ctx->ws<BMeta>(WS_B_META, 1);
-    unsigned long long *words = ctx->ws<unsigned long long>(WS_B_WORDS, n_tiles * B_WORDS);
-    long long *tile_cnt = ctx->ws<long long>(WS_B_TCNT, n_tiles + 1);
-    long long *tile_base = ctx->ws<long long>(WS_B_TBASE, n_tiles + 1);
     HIP_TRY(hipMemsetAsync(m, 0, sizeof *m, st));
-    HIP_TRY(hipMemsetAsync(tile_cnt + n_tiles, 0, sizeof(long long), st));
     const int vec = (((uintptr_t)dh->type | (uintptr_t)dh->f | (uintptr_t)dh->value | (uintptr_t)dh->value2) & 15) == 0;
-    const int g = grid_for(n_tiles, 1, 2048);
-    k_bank_flag<<<g, 256, 0, st>>>(dh->type, dh->f, n, vec, words, tile_cnt);
-    excl_scan(ctx, tile_cnt, tile_base, n_tiles + 1, st);
-    long long R = 0;
-    HIP_TRY(hipMemcpyAsync(&R, tile_base + n_tiles, sizeof R, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    const RowSel<1> sel = select_rows<1>(
+        ctx, {WS_B_WORDS, WS_B_TCNT, WS_B_TBASE, WS_B_TMP}, n, 2 * RS_TILE, RS_WORDS,
+        [&](int g, unsigned long long *words, long long *tile_cnt) {
+            k_bank_flag<<<g, 256, 0, st>>>(dh->type, dh->f, n, vec, words, tile_cnt);
+        }, st);
+    const long long R = sel.count[0];
     res->read_count = R;
     if (n_reads) *n_reads = R;
-    if (R == 0) { elapsed(); return; }
+    if (R == 0) { res->device_ms = timer.stop(); return; }
     if (R >= 0x7fffffffLL) throw_jh(JH_EUNSUPPORTED, "bank: more than 2^31 - 2 reads");
     if (half > 0 && !dh->aux) throw_jh(JH_EINVAL, "bank: n_aux > 0 without aux");
 
@@ -602,8 +518,9 @@ void bank_check(jh_ctx *ctx, const jh_history *dh, const jh_bank_opts *opts, jh_
     unsigned long long *bad = ctx->ws<unsigned long long>(WS_B_BAD, R);
     int *cls = ctx->ws<int>(WS_B_CLS, R);
     HIP_TRY(hipMemsetAsync(cnt + R, 0, sizeof(int64_t), st));
-    k_bank_compact<<<g, 256, 0, st>>>(dh->value, dh->value2, n, vec, words, tile_base, half, row, start, cnt, m);
-    excl_scan(ctx, cnt, off, R + 1, st);
+    k_bank_compact<<<sel.grid, 256, 0, st>>>(dh->value, dh->value2, n, vec, sel.words[0], sel.base[0], half, row, start,
+                                             cnt, m);
+    excl_sum(ctx, WS_B_TMP, as_input(cnt), off, (int)(R + 1), st);
     struct { BMeta m; long long E; } hb;
     HIP_TRY(hipMemcpyAsync(&hb.m, m, sizeof hb.m, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(&hb.E, off + R, sizeof hb.E, hipMemcpyDeviceToHost, st));
@@ -657,5 +574,5 @@ void bank_check(jh_ctx *ctx, const jh_history *dh, const jh_bank_opts *opts, jh_
     res->first_error_row = ho.first_error_row;
     if (ho.unknown > 0) { res->valid = JH_UNKNOWN; res->cause = JH_CAUSE_OVERFLOW; }
     else res->valid = res->error_count ? JH_INVALID : JH_VALID;
-    elapsed();
+    res->device_ms = timer.stop();
 }

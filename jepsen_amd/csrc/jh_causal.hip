@@ -15,7 +15,8 @@
 // Pipeline:
 //   1. k_cr_flag      type / f: the :invoke / :ok write rows and the :ok read
 //                     rows as ballot words (word j = rows 64 j .. 64 j + 63) and
-//                     their numbers per 2048-row tile; exclusive scans
+//                     their numbers per 2048-row tile; exclusive scans (the
+//                     host side and the per-wave prefix are row_select.h)
 //      k_cr_compact   the flagged rows in history order from the ballot words
 //                     (no atomic): writes as (key | ok << 31, value), reads as
 //                     (key, row, first element, count), ranges bounds-checked
@@ -39,12 +40,9 @@
 //                     k_cr_key<LIST> reruns the failing reads of the invalid
 //                     keys and lists the clear bits, one segmented radix sort
 //                     puts each read's values in ascending order.
-#include "jh_internal.h"
-#include <hipcub/hipcub.hpp>
-#include <algorithm>
+#include "row_select.h"
 
 namespace {
-constexpr int T_INVOKE = 0, T_OK = 1;
 constexpr int C_STEPS = 8;                    // rows per thread per tile
 constexpr int C_TILE = 256 * C_STEPS;         // rows per tile (2048)
 constexpr int C_WORDS = C_TILE / 64;          // ballot words per tile and kind (32)
@@ -124,16 +122,9 @@ __global__ void __launch_bounds__(256) k_cr_compact(const int64_t *__restrict__ 
     const int64_t n_tiles = (n + C_TILE - 1) / C_TILE;
     unsigned long long ent = 0;
     for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const unsigned long long w = lane < C_WORDS ? words[tile * C_WORDS + lane] : 0;
-        unsigned inc = __popcll(w);
-        const unsigned own = inc;
-#pragma unroll
-        for (int dd = 1; dd < 64; dd <<= 1) {
-            const unsigned o = __shfl_up(inc, dd);
-            if (lane >= dd) inc += o;
-        }
-        const unsigned excl = inc - own;
-        if (__shfl(inc, 63) == 0) continue;                   // no such row in this tile
+        unsigned long long w;
+        unsigned excl;
+        if (rs_word_prefix<C_WORDS>(words + tile * C_WORDS, lane, w, excl) == 0) continue;   // no such row in this tile
         const long long base = tile_base[tile];
 #pragma unroll
         for (int u = 0; u < C_STEPS; u++) {
@@ -510,27 +501,6 @@ int bits_of(unsigned long long x) {
     return b;
 }
 
-void excl_scan(jh_ctx *ctx, const long long *in, long long *out, int64_t cnt, hipStream_t st) {
-    size_t tb = 0;
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, in, out, (int)cnt, st));
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(ctx->ws<char>(WS_CR_TMP, tb), tb, in, out, (int)cnt, st));
-}
-
-template <class V>
-void sort_by_key(jh_ctx *ctx, const uint32_t *kin, uint32_t *kout, const V *vin, V *vout, int64_t cnt, int end_bit,
-                 hipStream_t st) {
-    size_t tb = 0;
-    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, kin, kout, vin, vout, (int)cnt, 0, end_bit, st));
-    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(ctx->ws<char>(WS_CR_TMP, tb), tb, kin, kout, vin, vout, (int)cnt, 0, end_bit, st));
-}
-
-CMeta read_meta(const CMeta *m, hipStream_t st) {
-    CMeta h;
-    HIP_TRY(hipMemcpyAsync(&h, m, sizeof h, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return h;
-}
-
 }  // namespace
 
 void causal_reverse_check(jh_ctx *ctx, const jh_history *dh, const jh_causal_reverse_opts *opts,
@@ -547,35 +517,21 @@ void causal_reverse_check(jh_ctx *ctx, const jh_history *dh, const jh_causal_rev
     if (n == 0) return;
     if (K > (int64_t)KEYMASK) throw_jh(JH_EUNSUPPORTED, "causal-reverse: more than 2^31 - 1 keys");
     if (n > 0x7fffffff00LL) throw_jh(JH_EUNSUPPORTED, "causal-reverse: more than 2^39 rows");
-    HIP_TRY(hipEventRecord(ctx->ev[0], st));
-    auto elapsed = [&] {
-        HIP_TRY(hipEventRecord(ctx->ev[1], st));
-        HIP_TRY(hipEventSynchronize(ctx->ev[1]));
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
-        res->device_ms = ms;
-    };
+    DeviceTimer timer{ctx, st};
+    timer.start();
 
     // 1. the writes and the reads, in history order
-    const int64_t n_tiles = (n + C_TILE - 1) / C_TILE;
     CMeta *m = ctx->ws<CMeta>(WS_CR_META, 1);
-    unsigned long long *words = ctx->ws<unsigned long long>(WS_CR_WORDS, 2 * n_tiles * C_WORDS);
-    unsigned long long *words_r = words, *words_w = words + n_tiles * C_WORDS;
-    long long *tile_cnt = ctx->ws<long long>(WS_CR_TCNT, 2 * (n_tiles + 1));
-    long long *tile_base = ctx->ws<long long>(WS_CR_TBASE, 2 * (n_tiles + 1));
-    long long *cnt_r = tile_cnt, *cnt_w = tile_cnt + n_tiles + 1;
-    long long *base_r = tile_base, *base_w = tile_base + n_tiles + 1;
     k_cr_meta_init<<<1, 1, 0, st>>>(m);
-    HIP_TRY(hipMemsetAsync(cnt_r + n_tiles, 0, sizeof(long long), st));
-    HIP_TRY(hipMemsetAsync(cnt_w + n_tiles, 0, sizeof(long long), st));
-    const int g = grid_for(n_tiles, 1, 2048);
-    k_cr_flag<<<g, 256, 0, st>>>(dh->type, dh->f, n, words_r, words_w, cnt_r, cnt_w);
-    excl_scan(ctx, cnt_r, base_r, n_tiles + 1, st);
-    excl_scan(ctx, cnt_w, base_w, n_tiles + 1, st);
-    long long R = 0, W = 0;
-    HIP_TRY(hipMemcpyAsync(&R, base_r + n_tiles, sizeof R, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(&W, base_w + n_tiles, sizeof W, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    const RowSel<2> sel = select_rows<2>(
+        ctx, {WS_CR_WORDS, WS_CR_TCNT, WS_CR_TBASE, WS_CR_TMP}, n, C_TILE, C_WORDS,
+        [&](int g, unsigned long long *words, long long *tile_cnt) {      // kind 0: reads, kind 1: writes
+            const int64_t n_tiles = (n + C_TILE - 1) / C_TILE;
+            k_cr_flag<<<g, 256, 0, st>>>(dh->type, dh->f, n, words, words + n_tiles * C_WORDS, tile_cnt,
+                                         tile_cnt + n_tiles + 1);
+        }, st);
+    const int g = sel.grid;
+    const long long R = sel.count[0], W = sel.count[1];
     res->read_count = R;
     if (R > C_MAX_COUNT) throw_jh(JH_EUNSUPPORTED, "causal-reverse: more than 2^31 - 2 reads");
     if (W > C_MAX_COUNT) throw_jh(JH_EUNSUPPORTED, "causal-reverse: more than 2^31 - 2 writes");
@@ -588,12 +544,12 @@ void causal_reverse_check(jh_ctx *ctx, const jh_history *dh, const jh_causal_rev
     int64_t *rrow = ctx->ws<int64_t>(WS_CR_RROW, 3 * R), *rstart = rrow + R, *rcnt = rrow + 2 * R;
     const int64_t Kc = keyed ? K : 0;
     if (W > 0)
-        k_cr_compact<1><<<g, 256, 0, st>>>(dh->type, dh->key, dh->value, dh->value2, n, Kc, dh->n_aux, words_w, base_w,
+        k_cr_compact<1><<<g, 256, 0, st>>>(dh->type, dh->key, dh->value, dh->value2, n, Kc, dh->n_aux, sel.words[1], sel.base[1],
                                            wkey, wval, nullptr, nullptr, m);
     if (R > 0)
-        k_cr_compact<0><<<g, 256, 0, st>>>(dh->type, dh->key, dh->value, dh->value2, n, Kc, dh->n_aux, words_r, base_r,
+        k_cr_compact<0><<<g, 256, 0, st>>>(dh->type, dh->key, dh->value, dh->value2, n, Kc, dh->n_aux, sel.words[0], sel.base[0],
                                            rkey, rrow, rstart, rcnt, m);
-    CMeta mh = read_meta(m, st);
+    CMeta mh = fetch(m, st);
     if (mh.bad_key) throw_jh(JH_EINVAL, "causal-reverse: a key outside [0, n_keys)");
     if (mh.bad_range) throw_jh(JH_EINVAL, "causal-reverse: a read's range leaves [0, n_aux) or has a negative count");
     if (mh.unsup_key)
@@ -607,10 +563,10 @@ void causal_reverse_check(jh_ctx *ctx, const jh_history *dh, const jh_causal_rev
     const uint32_t *rk_sorted = rkey;
     if (K > 1) {
         const int kb = bits_of((unsigned long long)(K - 1));
-        if (W > 0) { sort_by_key(ctx, wkey, wkey_s, wval, wval_s, W, kb, st); wk = wkey_s; wv = wval_s; }
+        if (W > 0) { sort_pairs(ctx, WS_CR_TMP, wkey, wkey_s, wval, wval_s, (int)W, kb, st); wk = wkey_s; wv = wval_s; }
         if (R > 0) {
             k_cr_iota<<<grid_for(R, 256, 2048), 256, 0, st>>>(rperm, R);
-            sort_by_key(ctx, rkey, rkey_s, rperm, rperm_s, R, kb, st);
+            sort_pairs(ctx, WS_CR_TMP, rkey, rkey_s, rperm, rperm_s, (int)R, kb, st);
             rp = rperm_s; rk_sorted = rkey_s;
         }
     }
@@ -635,7 +591,7 @@ void causal_reverse_check(jh_ctx *ctx, const jh_history *dh, const jh_causal_rev
     if (path != 2) {
         k_cr_key<true, false><<<gkey, KT, 0, st>>>(woff, roff, wk, wv, rp, rrow, rstart, rcnt, dh->aux, K, tier, nullptr,
                                                    nullptr, kv, exp, miss, eflag, nullptr, 0, nullptr, m);
-        mh = read_meta(m, st);
+        mh = fetch(m, st);
         if (mh.n_over && path == 1)
             throw_jh(JH_EINVAL, "causal-reverse on-chip path: a key with more than JH_CR_LDS_VALUES distinct values");
         global = mh.n_over > 0;
@@ -646,10 +602,8 @@ void causal_reverse_check(jh_ctx *ctx, const jh_history *dh, const jh_causal_rev
         long long *sbytes = ctx->ws<long long>(WS_CR_SOFF, 2 * (K + 1));
         soff = sbytes + K + 1;
         k_cr_sizes<<<gk, 256, 0, st>>>(woff, tier, K, sbytes);
-        excl_scan(ctx, sbytes, soff, K + 1, st);
-        long long total = 0;
-        HIP_TRY(hipMemcpyAsync(&total, soff + K, sizeof total, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
+        excl_sum(ctx, WS_CR_TMP, as_input(sbytes), soff, (int)(K + 1), st);
+        const long long total = fetch(soff + K, st);
         if (total > JH_CR_SCRATCH_MAX)
             throw_jh(JH_ENOMEM, "causal-reverse global tier: the value tables pass JH_CR_SCRATCH_MAX bytes");
         scratch = ctx->ws<char>(WS_CR_SCRATCH, (size_t)total);
@@ -659,12 +613,12 @@ void causal_reverse_check(jh_ctx *ctx, const jh_history *dh, const jh_causal_rev
     res->path = global ? 2 : 1;
 
     // 4. totals, and the outputs in history order
-    excl_scan(ctx, eflag, eidx, R + 1, st);
-    excl_scan(ctx, miss, moff, R + 1, st);
+    excl_sum(ctx, WS_CR_TMP, as_input(eflag), eidx, (int)(R + 1), st);
+    excl_sum(ctx, WS_CR_TMP, as_input(miss), moff, (int)(R + 1), st);
     long long E = 0, MT = 0;
     HIP_TRY(hipMemcpyAsync(&E, eidx + R, sizeof E, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(&MT, moff + R, sizeof MT, hipMemcpyDeviceToHost, st));
-    mh = read_meta(m, st);
+    mh = fetch(m, st);
     res->error_count = E;
     res->missing_total = MT;
     res->invalid_keys = (int64_t)mh.invalid_keys;
@@ -673,7 +627,7 @@ void causal_reverse_check(jh_ctx *ctx, const jh_history *dh, const jh_causal_rev
     if (key_valid) HIP_TRY(hipMemcpyAsync(key_valid, kv, sizeof(int32_t) * K, hipMemcpyDeviceToHost, st));
     if (E == 0) {
         HIP_TRY(hipStreamSynchronize(st));
-        elapsed();
+        res->device_ms = timer.stop();
         return;
     }
     const long long ecap = errors_out ? std::min<long long>(E, std::max<int64_t>(err_cap, 0)) : 0;
@@ -685,7 +639,7 @@ void causal_reverse_check(jh_ctx *ctx, const jh_history *dh, const jh_causal_rev
         k_cr_emit<<<grid_for(R, 256, 2048), 256, 0, st>>>(rkey, rrow, exp, miss, eidx, moff, R, ecap,
                                                           std::min<long long>(mcap, C_MAX_COUNT), out, seg, seg + E, m);
         if (ecap > 0) HIP_TRY(hipMemcpyAsync(errors_out, out, sizeof(int64_t) * 5 * ecap, hipMemcpyDeviceToHost, st));
-        mh = read_meta(m, st);
+        mh = fetch(m, st);
         if (mcap > 0) {
             // the reads that start below mcap are listed whole: at most mcap + one key's values
             if (mcap > C_MAX_COUNT || mh.list_end > (unsigned long long)C_MAX_COUNT)
@@ -697,14 +651,10 @@ void causal_reverse_check(jh_ctx *ctx, const jh_history *dh, const jh_causal_rev
             if (global)
                 k_cr_key<false, true><<<gkey, KT, 0, st>>>(woff, roff, wk, wv, rp, rrow, rstart, rcnt, dh->aux, K, tier,
                                                            scratch, soff, kv, exp, miss, eflag, moff, mcap, mbuf, m);
-            size_t tb = 0;
-            HIP_TRY(hipcub::DeviceSegmentedRadixSort::SortKeys(nullptr, tb, mbuf, mbuf_s, (int)L, (int)mh.n_seg, seg,
-                                                               seg + E, 0, 64, st));
-            HIP_TRY(hipcub::DeviceSegmentedRadixSort::SortKeys(ctx->ws<char>(WS_CR_TMP, tb), tb, mbuf, mbuf_s, (int)L,
-                                                               (int)mh.n_seg, seg, seg + E, 0, 64, st));
+            seg_sort_keys(ctx, WS_CR_TMP, mbuf, mbuf_s, (int)L, (int)mh.n_seg, seg, seg + E, st);
             HIP_TRY(hipMemcpyAsync(missing_out, mbuf_s, sizeof(int64_t) * mcap, hipMemcpyDeviceToHost, st));
         }
     }
     HIP_TRY(hipStreamSynchronize(st));
-    elapsed();
+    res->device_ms = timer.stop();
 }

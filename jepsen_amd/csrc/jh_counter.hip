@@ -32,8 +32,7 @@
 // round 3 folds the reduce pass into the pack. (A single-pass decoupled
 // look-back scan over the 49 K tiles was measured at 20.8 ms on MI355X: the
 // tile-to-tile look-back chain is serial latency across XCDs.)
-#include "jh_internal.h"
-#include <hipcub/hipcub.hpp>
+#include "jh_prims.h"
 
 namespace {
 
@@ -72,7 +71,6 @@ static_assert(SPILL_LANES >= 1 && SPILL_LANES <= 256 && (SPILL_LANES & (SPILL_LA
 #define PACK_BARRIER() __syncthreads()
 #endif
 
-constexpr int T_INVOKE = 0, T_OK = 1, T_FAIL = 2, T_INFO = 3;
 constexpr int CHUNK = 2048, HSLOTS = 1024;
 
 struct CntMeta {
@@ -827,10 +825,7 @@ void counter_check(jh_ctx *ctx, const jh_history *dh, int64_t *reads_out, int64_
     int32_t *rd_row = ctx->ws<int32_t>(WS_C_IDX, n);
     int64_t *rd_hi = ctx->ws<int64_t>(WS_C_HI, n);
     int64_t *lo_at = ctx->ws<int64_t>(WS_C_LO, n);
-    size_t tb = 0;
-    HIP_TRY(hipcub::DeviceScan::ExclusiveScan(nullptr, tb, agg, pre, CntSumOp(), CntAcc{0, 0, 0, 0}, (int)n_tiles, st));
-    void *tmp = ctx->ws<char>(WS_S_TMP, tb);
-    HIP_TRY(hipcub::DeviceScan::ExclusiveScan(tmp, tb, agg, pre, CntSumOp(), CntAcc{0, 0, 0, 0}, (int)n_tiles, st));
+    excl_scan(ctx, WS_S_TMP, agg, pre, CntSumOp(), CntAcc{0, 0, 0, 0}, (int)n_tiles, st);
     k_cnt_tile_scan<<<(unsigned)((n_tiles + TS_TILES - 1) / TS_TILES), 256, 0, st>>>(cw, pair, dh->value, n, n_tiles, pre,
                                                                                       rd_row, rd_hi, lo_at, total, m);
     // the triples of every :ok :read (their count stays on the device: the

@@ -560,24 +560,12 @@ int bits_of(u64 x) {
     return b;
 }
 
-YMeta read_meta(const YMeta *m, hipStream_t st) {
-    YMeta h;
-    HIP_TRY(hipMemcpyAsync(&h, m, sizeof h, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return h;
-}
-
 // the words of `in` that are not holes, in order; returns their number
 long long select_edges(jh_ctx *ctx, const u64 *in, u64 *out, long long cnt, hipStream_t st) {
     if (cnt == 0) return 0;
     long long *d_n = (long long *)ctx->ws<long long>(WS_CY_SEL, 1);
-    size_t tb = 0;
-    HIP_TRY(hipcub::DeviceSelect::If(nullptr, tb, in, out, d_n, (int)cnt, NotHole(), st));
-    HIP_TRY(hipcub::DeviceSelect::If(tmp(ctx, tb), tb, in, out, d_n, (int)cnt, NotHole(), st));
-    long long got = 0;
-    HIP_TRY(hipMemcpyAsync(&got, d_n, sizeof got, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return got;
+    select_if(ctx, WS_CY_TMP, in, out, d_n, (int)cnt, NotHole(), st);
+    return fetch(d_n, st);
 }
 
 void init_result(jh_cycle_result *res) {
@@ -619,26 +607,20 @@ void scc_core(jh_ctx *ctx, int64_t n, const u64 *edges, long long E, int path, j
     int32_t *bs = ctx->ws<int32_t>(WS_CY_BS, n);
     k_cy_iota<<<g, 256, 0, st>>>(reach, n);
     if (E > 0) k_cy_reach<<<ge, 256, 0, st>>>(edges, E, reach, m);
-    size_t tb = 0;
-    HIP_TRY(hipcub::DeviceScan::InclusiveScan(nullptr, tb, reach, mx, hipcub::Max(), (int)n, st));
-    HIP_TRY(hipcub::DeviceScan::InclusiveScan(tmp(ctx, tb), tb, reach, mx, hipcub::Max(), (int)n, st));
+    incl_scan(ctx, WS_CY_TMP, reach, mx, hipcub::Max(), (int)n, st);
     k_cy_starts<<<g, 256, 0, st>>>(reach, mx, n, big);
-    HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, tb, big, bs, (int)n, st));
-    HIP_TRY(hipcub::DeviceScan::InclusiveSum(tmp(ctx, tb), tb, big, bs, (int)n, st));
-    int32_t nr32 = 0;
-    HIP_TRY(hipMemcpyAsync(&nr32, bs + (n - 1), sizeof nr32, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    const int64_t NR = nr32;
+    incl_sum(ctx, WS_CY_TMP, big, bs, (int)n, st);
+    const int64_t NR = fetch(bs + (n - 1), st);
     res->regions = NR;
     if (NR == 0) {
-        res->back_edges = (int64_t)read_meta(m, st).back;
+        res->back_edges = (int64_t)fetch(m, st).back;
         empty_outputs(n, out);
         return;
     }
     int32_t *rstart = ctx->ws<int32_t>(WS_CY_REG, 2 * NR), *rend = rstart + NR;
     k_cy_bounds<<<g, 256, 0, st>>>(mx, big, bs, n, rstart, rend);
     k_cy_region_stats<<<grid_for(NR, 256, 1024), 256, 0, st>>>(rstart, rend, NR, path == 2, m);
-    YMeta mh = read_meta(m, st);
+    YMeta mh = fetch(m, st);
     res->back_edges = (int64_t)mh.back;
     res->max_region = (int64_t)mh.max_region;
     res->global_regions = (int64_t)mh.global_regions;
@@ -656,9 +638,9 @@ void scc_core(jh_ctx *ctx, int64_t n, const u64 *edges, long long E, int path, j
     const u64 *fwd_s = fwd;
     if (EI > 0) {
         k_cy_swap<<<grid_for(EI, 256, 4096), 256, 0, st>>>(fwd, EI, bwd);
-        sort_keys(ctx, fwd, fraw, EI, eb, st);
+        sort_keys(ctx, WS_CY_TMP, fwd, fraw, (int)EI, eb, st);
         fwd_s = fraw;
-        sort_keys(ctx, bwd, bwd_s, EI, eb, st);
+        sort_keys(ctx, WS_CY_TMP, bwd, bwd_s, (int)EI, eb, st);
     }
     k_cy_csr<<<g, 256, 0, st>>>(fwd_s, EI, n, foff);
     k_cy_csr<<<g, 256, 0, st>>>(bwd_s, EI, n, boff);
@@ -680,7 +662,7 @@ void scc_core(jh_ctx *ctx, int64_t n, const u64 *edges, long long E, int path, j
     // 4. results
     u64 *keys = ctx->ws<u64>(WS_CY_KEYS, 2 * n), *keys_s = keys + n;
     k_cy_keys<true><<<g, 256, 0, st>>>(labels, sccsize, n, keys, m);
-    mh = read_meta(m, st);
+    mh = fetch(m, st);
     if (mh.over_work) throw_jh(JH_EUNSUPPORTED, "cycle: a region past the work cap JH_CY_WORK_MULT * (vertices + edges)");
     res->scc_count = (int64_t)mh.scc_count;
     res->scc_vertices = (int64_t)mh.scc_vertices;
@@ -697,7 +679,7 @@ void scc_core(jh_ctx *ctx, int64_t n, const u64 *edges, long long E, int path, j
     if (n_list == 0) return;
     const long long got = select_edges(ctx, keys, keys_s, n, st);          // the roots' keys
     if (got != S) throw_jh(JH_EDEVICE, "cycle: SCC roots and counts disagree");
-    sort_keys(ctx, keys_s, keys, S, eb, st);
+    sort_keys(ctx, WS_CY_TMP, keys_s, keys, (int)S, eb, st);
     std::vector<u64> hk(n_list);
     HIP_TRY(hipMemcpyAsync(hk.data(), keys, sizeof(u64) * n_list, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -711,28 +693,15 @@ void scc_core(jh_ctx *ctx, int64_t n, const u64 *edges, long long E, int path, j
     int32_t *rows = ctx->ws<int32_t>(WS_CY_VALS, 3 * n), *rows_m = rows + n, *rows_s = rows + 2 * n;
     k_cy_iota<<<g, 256, 0, st>>>(rows, n);
     long long *d_n = ctx->ws<long long>(WS_CY_SEL, 1);
-    HIP_TRY(hipcub::DeviceSelect::If(nullptr, tb, rows, rows_m, d_n, (int)n, Flag64{keys}, st));
-    HIP_TRY(hipcub::DeviceSelect::If(tmp(ctx, tb), tb, rows, rows_m, d_n, (int)n, Flag64{keys}, st));
+    select_if(ctx, WS_CY_TMP, rows, rows_m, d_n, (int)n, Flag64{keys}, st);
     if (select_edges(ctx, keys, keys_s, n, st) != NV) throw_jh(JH_EDEVICE, "cycle: SCC members and counts disagree");
-    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, keys_s, keys, rows_m, rows_s, (int)NV, 0, eb, st));
-    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp(ctx, tb), tb, keys_s, keys, rows_m, rows_s, (int)NV, 0, eb, st));
+    sort_pairs(ctx, WS_CY_TMP, keys_s, keys, rows_m, rows_s, (int)NV, eb, st);
     std::vector<int32_t> hr(n_rows);
     HIP_TRY(hipMemcpyAsync(hr.data(), rows_s, sizeof(int32_t) * n_rows, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     for (long long i = 0; i < n_rows; i++) out.scc_rows[i] = hr[i];
 }
 
-struct Timer {
-    jh_ctx *ctx; hipStream_t st; jh_cycle_result *res;
-    Timer(jh_ctx *c, hipStream_t s, jh_cycle_result *r) : ctx(c), st(s), res(r) { HIP_TRY(hipEventRecord(ctx->ev[0], st)); }
-    void stop() {
-        HIP_TRY(hipEventRecord(ctx->ev[1], st));
-        HIP_TRY(hipEventSynchronize(ctx->ev[1]));
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
-        res->device_ms = ms;
-    }
-};
 
 }  // namespace
 
@@ -746,13 +715,14 @@ void scc_check(jh_ctx *ctx, int64_t n, const int64_t *src, const int64_t *dst, i
     res->edge_count[3] = n_edges;
     empty_outputs(n, out);
     if (n == 0) return;
-    Timer timer(ctx, st, res);
+    DeviceTimer timer{ctx, st};
+    timer.start();
     YMeta *m = ctx->ws<YMeta>(WS_CY_META, 1);
     k_cy_meta_init<<<1, 1, 0, st>>>(m);
     u64 *edges = ctx->ws<u64>(WS_CY_EDGES, n_edges);
     if (n_edges > 0) HIP_TRY(hipMemcpyAsync(edges, h.data(), sizeof(u64) * n_edges, hipMemcpyHostToDevice, st));
     scc_core(ctx, n, edges, n_edges, opts->path, res, out, m, st);
-    timer.stop();
+    res->device_ms = timer.stop();
 }
 
 void cycle_check(jh_ctx *ctx, const jh_history *dh, const jh_cycle_opts *opts, jh_cycle_result *res, const CycleOut &out,
@@ -766,7 +736,8 @@ void cycle_check(jh_ctx *ctx, const jh_history *dh, const jh_cycle_opts *opts, j
     res->edge_count[3] = opts->n_extra;
     empty_outputs(n, out);
     if (n == 0) return;
-    Timer timer(ctx, st, res);
+    DeviceTimer timer{ctx, st};
+    timer.start();
     YMeta *m = ctx->ws<YMeta>(WS_CY_META, 1);
     k_cy_meta_init<<<1, 1, 0, st>>>(m);
     const int g = grid_for(n + 1, 256, 2048);
@@ -783,10 +754,10 @@ void cycle_check(jh_ctx *ctx, const jh_history *dh, const jh_cycle_opts *opts, j
         cw = cr + (n + 1); ro = cr + 2 * (n + 1); wo = cr + 3 * (n + 1);
         k_cy_txn<false><<<g, 256, 0, st>>>(dh->process, dh->type, dh->value, dh->value2, dh->aux, n, dh->n_aux / 3, cr, cw,
                                            nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, m);
-        excl_sum(ctx, cr, ro, n + 1, st);
-        excl_sum(ctx, cw, wo, n + 1, st);
+        excl_sum(ctx, WS_CY_TMP, as_input(cr), ro, (int)(n + 1), st);
+        excl_sum(ctx, WS_CY_TMP, as_input(cw), wo, (int)(n + 1), st);
     }
-    YMeta mh = read_meta(m, st);
+    YMeta mh = fetch(m, st);
     if (mh.bad_type) throw_jh(JH_EINVAL, "cycle: a :type outside 0..3");
     if (mh.bad_range) throw_jh(JH_EINVAL, "cycle: a txn's range leaves [0, n_aux / 3) or has a negative count");
     if (mh.unsup_mops) throw_jh(JH_EUNSUPPORTED, "cycle: a txn of more than JH_CY_MAX_MOPS micro-ops");
@@ -794,7 +765,7 @@ void cycle_check(jh_ctx *ctx, const jh_history *dh, const jh_cycle_opts *opts, j
     res->entries = (int64_t)mh.entries;
     auto unknown = [&](int cause, u64 row) {
         res->valid = JH_UNKNOWN; res->cause = cause; res->unknown_row = (int64_t)row;
-        timer.stop();
+        res->device_ms = timer.stop();
     };
 
     // pairs, process edges, realtime edge counts
@@ -804,9 +775,7 @@ void cycle_check(jh_ctx *ctx, const jh_history *dh, const jh_cycle_opts *opts, j
     const long long n_proc_slots = (an & JH_CY_PROCESS) ? n : 0;
     u64 *proc_raw = nullptr;
     if (pairs) {
-        size_t tb = 0;
-        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, pkey, pkey_s, prow, prow_s, (int)n, 0, 64, st));
-        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp(ctx, tb), tb, pkey, pkey_s, prow, prow_s, (int)n, 0, 64, st));
+        sort_pairs(ctx, WS_CY_TMP, pkey, pkey_s, prow, prow_s, (int)n, 64, st);
         // (process slots live in their own buffer until the total is known)
         proc_raw = ctx->ws<u64>(WS_CY_KEYS, n);
         k_cy_pair<<<g, 256, 0, st>>>(pkey_s, prow_s, dh->type, n, (an & JH_CY_PROCESS) ? 1 : 0, comp, proc_raw, m);
@@ -816,14 +785,12 @@ void cycle_check(jh_ctx *ctx, const jh_history *dh, const jh_cycle_opts *opts, j
         ip = ctx->ws<int32_t>(WS_CY_IP, 2 * (n + 1));
         int32_t *isinv = ip + (n + 1);
         k_cy_rt_key<<<g, 256, 0, st>>>(dh->process, dh->type, comp, n, rev, isinv, m);
-        mh = read_meta(m, st);
+        mh = fetch(m, st);
         if (mh.dbl_row != NONE) return unknown(JH_CAUSE_DOUBLE_INVOKE, mh.dbl_row);
         if (mh.orphan_row != NONE) return unknown(JH_CAUSE_ORPHAN, mh.orphan_row);
         if (mh.unmatched_row != NONE) return unknown(JH_CAUSE_UNMATCHED_INVOKE, mh.unmatched_row);
-        size_t tb = 0;
-        HIP_TRY(hipcub::DeviceScan::ExclusiveScan(nullptr, tb, rev, sufmin, hipcub::Min(), (int32_t)n, (int)n, st));
-        HIP_TRY(hipcub::DeviceScan::ExclusiveScan(tmp(ctx, tb), tb, rev, sufmin, hipcub::Min(), (int32_t)n, (int)n, st));
-        excl_sum(ctx, isinv, ip, n + 1, st);
+        excl_scan(ctx, WS_CY_TMP, rev, sufmin, hipcub::Min(), (int32_t)n, (int)n, st);
+        excl_sum(ctx, WS_CY_TMP, as_input(isinv), ip, (int)(n + 1), st);
         int32_t n_inv = 0;
         HIP_TRY(hipMemcpyAsync(&n_inv, ip + n, sizeof n_inv, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
@@ -831,7 +798,7 @@ void cycle_check(jh_ctx *ctx, const jh_history *dh, const jh_cycle_opts *opts, j
         long long *cnt = ctx->ws<long long>(WS_CY_CNT, 2 * (n + 1));
         rt_off = cnt + (n + 1);
         k_cy_rt_count<<<g, 256, 0, st>>>(dh->process, dh->type, comp, sufmin, ip, n, cnt, icomp);
-        excl_sum(ctx, cnt, rt_off, n + 1, st);
+        excl_sum(ctx, WS_CY_TMP, as_input(cnt), rt_off, (int)(n + 1), st);
         HIP_TRY(hipMemcpyAsync(&n_rt, rt_off + n, sizeof n_rt, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
     }
@@ -839,7 +806,7 @@ void cycle_check(jh_ctx *ctx, const jh_history *dh, const jh_cycle_opts *opts, j
     AppendPlan ap;
     if (an & JH_CY_APPEND) {
         ap = append_plan(ctx, dh, res, st);
-        if (ap.cause) { timer.stop(); return; }
+        if (ap.cause) { res->device_ms = timer.stop(); return; }
     }
     // monotonic-key: the sorted records and the number of its edges (jh_cycle_mono.hip)
     MonoPlan mp;
@@ -870,16 +837,14 @@ void cycle_check(jh_ctx *ctx, const jh_history *dh, const jh_cycle_opts *opts, j
         k_cy_txn<true><<<g, 256, 0, st>>>(dh->process, dh->type, dh->value, dh->value2, dh->aux, n, dh->n_aux / 3, ro, wo, rk,
                                           rv, rrow, wk, wv, wrow, whash, widx, m);
         if (W > 0) {
-            size_t tb = 0;
-            HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, whash, whash_s, widx, widx_s, (int)W, 0, 64, st));
-            HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp(ctx, tb), tb, whash, whash_s, widx, widx_s, (int)W, 0, 64, st));
+            sort_pairs(ctx, WS_CY_TMP, whash, whash_s, widx, widx_s, (int)W, 64, st);
         }
         k_cy_wr_join<<<grid_for(R, 256, 4096), 256, 0, st>>>(rk, rv, rrow, R, whash_s, widx_s, wk, wv, wrow, W, raw_wr, m);
         k_cy_wr_unknown<<<1, 1, 0, st>>>(ro, rk, rv, whash_s, widx_s, wk, wv, wrow, W, m);
     }
     if (!extra.empty())
         HIP_TRY(hipMemcpyAsync(raw_x, extra.data(), sizeof(u64) * extra.size(), hipMemcpyHostToDevice, st));
-    mh = read_meta(m, st);
+    mh = fetch(m, st);
     if (mh.multi_row != NONE) {
         res->unknown_key = mh.unknown_key; res->unknown_value = mh.unknown_value;
         res->unknown_rows[0] = mh.unknown_rows[0]; res->unknown_rows[1] = mh.unknown_rows[1];
@@ -891,5 +856,5 @@ void cycle_check(jh_ctx *ctx, const jh_history *dh, const jh_cycle_opts *opts, j
     u64 *edges = ctx->ws<u64>(WS_CY_EDGES, n_raw);
     const long long E = select_edges(ctx, raw, edges, n_raw, st);
     scc_core(ctx, n, edges, E, opts->path, res, out, m, st);
-    timer.stop();
+    res->device_ms = timer.stop();
 }

@@ -434,8 +434,8 @@ AppendPlan append_plan(jh_ctx *ctx, const jh_history *dh, jh_cycle_result *res, 
 
     // 1. records
     k_ap_txn<false><<<g, 256, 0, st>>>(a);
-    excl_sum(ctx, a.cr, a.ro, n + 1, st);
-    excl_sum(ctx, a.ca, a.ao, n + 1, st);
+    excl_sum(ctx, WS_CY_TMP, as_input(a.cr), a.ro, (int)(n + 1), st);
+    excl_sum(ctx, WS_CY_TMP, as_input(a.ca), a.ao, (int)(n + 1), st);
     HIP_TRY(hipMemcpyAsync(&a.R, a.ro + n, sizeof a.R, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(&a.A, a.ao + n, sizeof a.A, hipMemcpyDeviceToHost, st));
     AMeta mh = fetch(a.m, st);
@@ -467,9 +467,9 @@ AppendPlan append_plan(jh_ctx *ctx, const jh_history *dh, jh_cycle_result *res, 
     // 2. the longest read of every key; the tiles of the others
     if (R > 0) k_ap_best<<<gr, 256, 0, st>>>(a);
     k_ap_llen<<<gk, 256, 0, st>>>(a);
-    excl_sum(ctx, a.llen, a.loff, K + 1, st);
+    excl_sum(ctx, WS_CY_TMP, as_input(a.llen), a.loff, (int)(K + 1), st);
     k_ap_tiles<<<gr, 256, 0, st>>>(a);
-    excl_sum(ctx, a.tcnt, a.toff, R + 1, st);
+    excl_sum(ctx, WS_CY_TMP, as_input(a.tcnt), a.toff, (int)(R + 1), st);
     long long T = 0;
     HIP_TRY(hipMemcpyAsync(&T, a.toff + R, sizeof T, hipMemcpyDeviceToHost, st));
     a.NL = fetch(a.loff + K, st);
@@ -485,21 +485,18 @@ AppendPlan append_plan(jh_ctx *ctx, const jh_history *dh, jh_cycle_result *res, 
     // 4. positions and duplicates of every L_k; the reads' duplicates
     if (NL > 0) {
         k_ap_lrec<<<grid_for(NL, 256, 4096), 256, 0, st>>>(a);
-        sort_pairs(ctx, a.lhash, a.lhash_s, a.lidx, a.lidx_s, NL, st);
+        sort_pairs(ctx, WS_CY_TMP, a.lhash, a.lhash_s, a.lidx, a.lidx_s, (int)NL, 64, st);
         k_ap_ldup<<<grid_for(NL, 256, 4096), 256, 0, st>>>(a);
     }
     if (R > 0) {
         k_ap_rdup<<<gr, 256, 0, st>>>(a);
-        size_t tb = 0;
-        hipcub::CountingInputIterator<int32_t> iota(0);
-        HIP_TRY(hipcub::DeviceSelect::Flagged(nullptr, tb, iota, a.need, a.dlist, a.d_n, (int)R, st));
-        HIP_TRY(hipcub::DeviceSelect::Flagged(tmp(ctx, tb), tb, iota, a.need, a.dlist, a.d_n, (int)R, st));
+        select_flagged(ctx, WS_CY_TMP, hipcub::CountingInputIterator<int32_t>(0), a.need, a.dlist, a.d_n, (int)R, st);
         k_ap_direct<<<grid_for(R, 1, 1024), 256, 0, st>>>(a);
     }
 
     // 5. unique appends; the keys without a total order
     if (A > 0) {
-        sort_pairs(ctx, a.ahash, a.ahash_s, a.aidx, a.aidx_s, A, st);
+        sort_pairs(ctx, WS_CY_TMP, a.ahash, a.ahash_s, a.aidx, a.aidx_s, (int)A, 64, st);
         k_ap_adup<<<ga, 256, 0, st>>>(a);
     }
     k_ap_badkeys<<<gk, 256, 0, st>>>(a);
@@ -524,11 +521,11 @@ AppendPlan append_plan(jh_ctx *ctx, const jh_history *dh, jh_cycle_result *res, 
     // 6, 7. writers; the wr and ww slots; the rw runs
     if (R > 0) {
         k_ap_skey<<<gr, 256, 0, st>>>(a);
-        sort_pairs(ctx, a.skey, a.skey_s, a.sidx, a.sidx_s, R, st);
+        sort_pairs(ctx, WS_CY_TMP, a.skey, a.skey_s, a.sidx, a.sidx_s, (int)R, 64, st);
         k_ap_wr<<<gr, 256, 0, st>>>(a);
     }
     k_ap_ww<<<ga, 256, 0, st>>>(a);
-    excl_sum(ctx, a.rwcnt, a.rwoff, A + 1, st);
+    excl_sum(ctx, WS_CY_TMP, as_input(a.rwcnt), a.rwoff, (int)(A + 1), st);
     long long RW = 0;
     HIP_TRY(hipMemcpyAsync(&RW, a.rwoff + A, sizeof RW, hipMemcpyDeviceToHost, st));
     mh = fetch(a.m, st);

@@ -174,7 +174,7 @@ MonoPlan mono_plan(jh_ctx *ctx, const jh_history *dh, jh_cycle_result *res, hipS
 
     // 1. records
     k_mo_rows<false><<<g, 256, 0, st>>>(a);
-    excl_sum(ctx, a.cr, a.ro, n + 1, st);
+    excl_sum(ctx, WS_CY_TMP, as_input(a.cr), a.ro, (int)(n + 1), st);
     HIP_TRY(hipMemcpyAsync(&a.M, a.ro + n, sizeof a.M, hipMemcpyDeviceToHost, st));
     const MMeta mh = fetch(a.m, st);
     if (mh.bad_range) throw_jh(JH_EINVAL, "cycle: a map's pair range leaves [0, n_aux / 2) or has a negative count");
@@ -194,19 +194,17 @@ MonoPlan mono_plan(jh_ctx *ctx, const jh_history *dh, jh_cycle_result *res, hipS
     k_mo_rows<true><<<g, 256, 0, st>>>(a);
 
     // 2. the records in (k, v) order
-    sort_pairs(ctx, a.rv, a.t0, a.idx, a.idx_s, M, st);
+    sort_pairs(ctx, WS_CY_TMP, a.rv, a.t0, a.idx, a.idx_s, (int)M, 64, st);
     k_mo_gather_k<<<gm, 256, 0, st>>>(a);
-    sort_pairs(ctx, a.t1, a.sk, a.idx_s, a.idx2, M, st);
+    sort_pairs(ctx, WS_CY_TMP, a.t1, a.sk, a.idx_s, a.idx2, (int)M, 64, st);
     k_mo_gather<<<gm, 256, 0, st>>>(a);
 
     // 3-5. groups, the next group of every record, the edges' places
     k_mo_flag<<<gm, 256, 0, st>>>(a);
-    size_t tb = 0;
-    HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, tb, a.flag, a.gid, (int)M, st));
-    HIP_TRY(hipcub::DeviceScan::InclusiveSum(tmp(ctx, tb), tb, a.flag, a.gid, (int)M, st));
+    incl_sum(ctx, WS_CY_TMP, a.flag, a.gid, (int)M, st);
     k_mo_gstart<<<gm, 256, 0, st>>>(a);
     k_mo_cnt<<<gm, 256, 0, st>>>(a);
-    excl_sum(ctx, a.cnt, a.eoff, M + 1, st);
+    excl_sum(ctx, WS_CY_TMP, as_input(a.cnt), a.eoff, (int)(M + 1), st);
     const long long total = fetch(a.eoff + M, st);
     if (total > Y_MAX) throw_jh(JH_EUNSUPPORTED, "cycle: more than 2^31 - 2 vertices or edges");
     plan.records = M; plan.slots = total;

@@ -11,8 +11,8 @@
 // Pipeline:
 //   1. k_lf_flag       type / f in 16-byte row-pair loads: the :ok read rows
 //                      and the :invoke write rows as ballot words and their
-//                      numbers per 4096-row tile (jh_bank's scheme); exclusive
-//                      scans of the tile counts
+//                      numbers per 4096-row tile (jh_bank's scheme: row_select.h);
+//                      exclusive scans of the tile counts
 //      k_lf_compact    value / value2 of the flagged rows, in history order
 //                      from the ballot words (no atomic): reads as (row, first
 //                      pair, count), ranges bounds-checked; writes as (key,
@@ -40,15 +40,9 @@
 //                      group, stably sorted by slot; k_lf_pairs, one wave per
 //                      suspect over the later suspects of its group: counts,
 //                      exclusive sum, then the pairs in order up to fork_cap
-#include "jh_internal.h"
-#include <hipcub/hipcub.hpp>
-#include <algorithm>
+#include "row_select.h"
 
 namespace {
-constexpr int T_INVOKE = 0, T_OK = 1;
-constexpr int L_PAIRS = 8;                   // row pairs per thread per tile
-constexpr int L_TILE = 256 * L_PAIRS;        // row pairs per tile (4096 rows: LF_TILE in _abi.py)
-constexpr int L_WORDS = L_PAIRS * 4 * 2;     // ballot words per tile and kind (64)
 constexpr unsigned long long SIGN = 1ULL << 63;
 constexpr unsigned long long NONE = ~0ULL;
 constexpr unsigned CONFLICT = 1u << 31;      // cnt word: two distinct non-nil values seen
@@ -73,11 +67,6 @@ __global__ void k_lf_meta_init(LMeta *m) {
     m->ill1_row = m->ill2_row = m->mw_row = NONE;
 }
 
-__device__ __forceinline__ longlong2 l_ld_pair(const int64_t *__restrict__ c, int64_t i, int64_t n, bool vec) {
-    if (2 * i + 1 < n) return vec ? ((const longlong2 *)c)[i] : make_longlong2(c[2 * i], c[2 * i + 1]);
-    return make_longlong2(c[2 * i], 0);
-}
-
 // Clojure's floored mod / quot for 1 <= n <= 64
 __device__ __forceinline__ void floor_divmod(long long k, long long n, long long &q, int &r) {
     q = k / n;
@@ -87,53 +76,16 @@ __device__ __forceinline__ void floor_divmod(long long k, long long n, long long
 }
 
 // ---------------------------------------------------------------------------
-// 1. Tile = 256 threads x L_PAIRS row pairs, pair p0 + u * 256 + thread; word
-// ((tile * L_PAIRS + u) * 4 + wave) * 2 + h holds the ballot of row 2p + h over
-// the wave's 64 pairs. words / tile_cnt: reads first, then writes.
+// 1. the :ok read rows (kind 0) and the :invoke write rows (kind 1): row_select.h, pair layout
 __global__ void __launch_bounds__(256) k_lf_flag(const int64_t *__restrict__ type, const int64_t *__restrict__ f,
-                                                 int64_t n, int vec, unsigned long long *__restrict__ words_r,
-                                                 unsigned long long *__restrict__ words_w,
-                                                 long long *__restrict__ cnt_r, long long *__restrict__ cnt_w) {
-    __shared__ unsigned sh[8];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t np = (n + 1) / 2, n_tiles = (np + L_TILE - 1) / L_TILE;
-    for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const int64_t p0 = tile * L_TILE + threadIdx.x;
-        longlong2 t2[L_PAIRS], f2[L_PAIRS];
-#pragma unroll
-        for (int u = 0; u < L_PAIRS; u++) {
-            const int64_t p = p0 + u * 256;
-            if (p < np) { t2[u] = l_ld_pair(type, p, n, vec); f2[u] = l_ld_pair(f, p, n, vec); }
-            else { t2[u] = make_longlong2(-1, -1); f2[u] = t2[u]; }
-        }
-        unsigned cr = 0, cw = 0;
-#pragma unroll
-        for (int u = 0; u < L_PAIRS; u++) {
-            const int64_t p = p0 + u * 256;
-            const bool in0 = p < np, in1 = 2 * p + 1 < n;
-            const bool r0 = in0 && t2[u].x == T_OK && f2[u].x == JH_F_READ;
-            const bool r1 = in1 && t2[u].y == T_OK && f2[u].y == JH_F_READ;
-            const bool w0 = in0 && t2[u].x == T_INVOKE && f2[u].x == JH_F_WRITE;
-            const bool w1 = in1 && t2[u].y == T_INVOKE && f2[u].y == JH_F_WRITE;
-            const unsigned long long b0 = __ballot(r0), b1 = __ballot(r1), c0 = __ballot(w0), c1 = __ballot(w1);
-            cr += __popcll(b0) + __popcll(b1);
-            cw += __popcll(c0) + __popcll(c1);
-            const int64_t wi = ((tile * L_PAIRS + u) * 4 + wave) * 2;
-            if (lane < 2) { words_r[wi + lane] = lane ? b1 : b0; words_w[wi + lane] = lane ? c1 : c0; }
-        }
-        if (lane == 0) { sh[wave] = cr; sh[4 + wave] = cw; }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            cnt_r[tile] = (long long)(sh[0] + sh[1] + sh[2] + sh[3]);
-            cnt_w[tile] = (long long)(sh[4] + sh[5] + sh[6] + sh[7]);
-        }
-        __syncthreads();
-    }
+                                                 int64_t n, int vec, unsigned long long *__restrict__ words,
+                                                 long long *__restrict__ tile_cnt) {
+    rs_flag_pairs<2>(type, f, n, vec, words, tile_cnt, [](int k, const long long &t, const long long &ff) {
+        return k ? t == T_INVOKE && ff == JH_F_WRITE : t == T_OK && ff == JH_F_READ;
+    });
 }
 
-// The flagged rows of one kind, in history order. Every wave scans the tile's
-// 64 ballot words itself: the exclusive prefix of their popcounts at word
-// 2 * (u * 4 + wave) is where the wave's rows of step u go.
+// The flagged rows of one kind, in history order.
 // WR = 0: reads -> (row, first pair, count), a[o] = row, b[o] = start, c[o] = count.
 // WR = 1: writes -> a[o] = key, b[o] = row; min / max key into the meta.
 template <int WR>
@@ -143,52 +95,26 @@ __global__ void __launch_bounds__(256) k_lf_compact(const int64_t *__restrict__ 
                                                     int64_t *__restrict__ a, int64_t *__restrict__ b,
                                                     int64_t *__restrict__ c, LMeta *m) {
     __shared__ unsigned long long shr[4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const unsigned long long lt = (1ULL << lane) - 1;
-    const int64_t np = (n + 1) / 2, n_tiles = (np + L_TILE - 1) / L_TILE;
     unsigned long long kmin = NONE, kmax = 0;
-    for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const unsigned long long w = words[tile * L_WORDS + lane];
-        unsigned inc = __popcll(w);
-        const unsigned own = inc;
+    rs_compact_pairs(n, words, tile_base, [&](int64_t p, bool r0, bool r1, long long o) {
+        const longlong2 v2 = ld_pair(value, p, n, vec);
+        longlong2 c2 = make_longlong2(0, 0);
+        if (!WR) c2 = ld_pair(value2, p, n, vec);
 #pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const unsigned o = __shfl_up(inc, d);
-            if (lane >= d) inc += o;
-        }
-        const unsigned excl = inc - own;
-        if (__shfl(inc, 63) == 0) continue;                   // no such row in this tile
-        const long long base = tile_base[tile];
-        const int64_t p0 = tile * L_TILE + threadIdx.x;
-#pragma unroll
-        for (int u = 0; u < L_PAIRS; u++) {
-            const int wi = 2 * (u * 4 + wave);
-            const unsigned long long b0 = __shfl(w, wi), b1 = __shfl(w, wi + 1);
-            const unsigned at = __shfl(excl, wi);
-            if ((b0 | b1) == 0) continue;                     // wave-uniform
-            const int64_t p = p0 + u * 256;
-            const bool r0 = (b0 >> lane) & 1, r1 = (b1 >> lane) & 1;
-            if (!(r0 || r1)) continue;                        // nothing below is cross-lane
-            const longlong2 v2 = l_ld_pair(value, p, n, vec);
-            longlong2 c2 = make_longlong2(0, 0);
-            if (!WR) c2 = l_ld_pair(value2, p, n, vec);
-            long long o = base + at + __popcll(b0 & lt) + __popcll(b1 & lt);
-#pragma unroll
-            for (int h = 0; h < 2; h++) {
-                if (!(h ? r1 : r0)) continue;
-                long long v = h ? v2.y : v2.x, cc = h ? c2.y : c2.x;
-                if (WR) {
-                    a[o] = v; b[o] = 2 * p + h;
-                    kmin = min(kmin, ord(v)); kmax = max(kmax, ord(v));
-                } else {
-                    if (v == JH_NIL && cc == 0) v = 0;        // a nil :value: no pairs
-                    else if (v < 0 || cc < 0 || v > half || cc > half - v) { atomicOr(&m->bad_range, 1u); v = 0; cc = 0; }
-                    a[o] = 2 * p + h; b[o] = v; c[o] = cc;
-                }
-                o++;
+        for (int h = 0; h < 2; h++) {
+            if (!(h ? r1 : r0)) continue;
+            long long v = h ? v2.y : v2.x, cc = h ? c2.y : c2.x;
+            if (WR) {
+                a[o] = v; b[o] = 2 * p + h;
+                kmin = min(kmin, ord(v)); kmax = max(kmax, ord(v));
+            } else {
+                if (v == JH_NIL && cc == 0) v = 0;        // a nil :value: no pairs
+                else if (v < 0 || cc < 0 || v > half || cc > half - v) { atomicOr(&m->bad_range, 1u); v = 0; cc = 0; }
+                a[o] = 2 * p + h; b[o] = v; c[o] = cc;
             }
+            o++;
         }
-    }
+    });
     if (WR) {
         kmin = block_reduce256(kmin, RedMin(), shr);
         kmax = block_reduce256(kmax, RedMax(), shr);
@@ -507,29 +433,6 @@ int bits_of(unsigned long long x) {
     return b;
 }
 
-template <class T>
-void excl_scan(jh_ctx *ctx, const T *in, T *out, int64_t cnt, hipStream_t st) {
-    size_t tb = 0;
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, in, out, (int)cnt, st));
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(ctx->ws<char>(WS_LF_TMP, tb), tb, in, out, (int)cnt, st));
-}
-
-// stable sort of (key, idx) pairs; returns through the double buffers
-template <class K>
-void sort_pairs(jh_ctx *ctx, hipcub::DoubleBuffer<K> &k, hipcub::DoubleBuffer<uint32_t> &v, int64_t cnt, int end_bit,
-                hipStream_t st) {
-    size_t tb = 0;
-    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, k, v, (int)cnt, 0, end_bit, st));
-    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(ctx->ws<char>(WS_LF_TMP, tb), tb, k, v, (int)cnt, 0, end_bit, st));
-}
-
-LMeta read_meta(const LMeta *m, hipStream_t st) {
-    LMeta h;
-    HIP_TRY(hipMemcpyAsync(&h, m, sizeof h, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return h;
-}
-
 }  // namespace
 
 void long_fork_check(jh_ctx *ctx, const jh_history *dh, const jh_long_fork_opts *opts, jh_long_fork_result *res,
@@ -544,39 +447,23 @@ void long_fork_check(jh_ctx *ctx, const jh_history *dh, const jh_long_fork_opts 
     if (dh->n_aux < 0 || (dh->n_aux & 1)) throw_jh(JH_EINVAL, "long-fork: n_aux must be even and >= 0 (pairs)");
     if (n == 0) return;
     if (n > 0x7fffffff00LL) throw_jh(JH_EUNSUPPORTED, "long-fork: more than 2^39 rows");
-    HIP_TRY(hipEventRecord(ctx->ev[0], st));
-    auto elapsed = [&] {
-        HIP_TRY(hipEventRecord(ctx->ev[1], st));
-        HIP_TRY(hipEventSynchronize(ctx->ev[1]));
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
-        res->device_ms = ms;
-    };
+    DeviceTimer timer{ctx, st};
+    timer.start();
     const int64_t half = dh->n_aux / 2;
     int logL = 0;
     while (logL < 4 && (2LL << logL) <= gn) logL++;               // L = 1, 2, 4, 8, 16 lanes per read: L <= n (< 2 L up to 16)
 
     // 1. the reads and the writes, in history order
-    const int64_t np = (n + 1) / 2, n_tiles = (np + L_TILE - 1) / L_TILE;
     LMeta *m = ctx->ws<LMeta>(WS_LF_META, 1);
-    unsigned long long *words = ctx->ws<unsigned long long>(WS_LF_WORDS, 2 * n_tiles * L_WORDS);
-    unsigned long long *words_r = words, *words_w = words + n_tiles * L_WORDS;
-    long long *tile_cnt = ctx->ws<long long>(WS_LF_TCNT, 2 * (n_tiles + 1));
-    long long *tile_base = ctx->ws<long long>(WS_LF_TBASE, 2 * (n_tiles + 1));
-    long long *cnt_r = tile_cnt, *cnt_w = tile_cnt + n_tiles + 1;
-    long long *base_r = tile_base, *base_w = tile_base + n_tiles + 1;
     k_lf_meta_init<<<1, 1, 0, st>>>(m);
-    HIP_TRY(hipMemsetAsync(cnt_r + n_tiles, 0, sizeof(long long), st));
-    HIP_TRY(hipMemsetAsync(cnt_w + n_tiles, 0, sizeof(long long), st));
     const int vec = (((uintptr_t)dh->type | (uintptr_t)dh->f | (uintptr_t)dh->value | (uintptr_t)dh->value2) & 15) == 0;
-    const int g = grid_for(n_tiles, 1, 2048);
-    k_lf_flag<<<g, 256, 0, st>>>(dh->type, dh->f, n, vec, words_r, words_w, cnt_r, cnt_w);
-    excl_scan(ctx, cnt_r, base_r, n_tiles + 1, st);
-    excl_scan(ctx, cnt_w, base_w, n_tiles + 1, st);
-    long long R = 0, W = 0;
-    HIP_TRY(hipMemcpyAsync(&R, base_r + n_tiles, sizeof R, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(&W, base_w + n_tiles, sizeof W, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    const RowSel<2> sel = select_rows<2>(
+        ctx, {WS_LF_WORDS, WS_LF_TCNT, WS_LF_TBASE, WS_LF_TMP}, n, 2 * RS_TILE, RS_WORDS,
+        [&](int g, unsigned long long *words, long long *tile_cnt) {
+            k_lf_flag<<<g, 256, 0, st>>>(dh->type, dh->f, n, vec, words, tile_cnt);
+        }, st);
+    const int g = sel.grid;
+    const long long R = sel.count[0], W = sel.count[1];
     res->reads_count = R;
     if (R > L_MAX_COUNT) throw_jh(JH_EUNSUPPORTED, "long-fork: more than 2^31 - 2 reads");
     if (W > L_MAX_COUNT) throw_jh(JH_EUNSUPPORTED, "long-fork: more than 2^31 - 2 write invocations");
@@ -591,7 +478,7 @@ void long_fork_check(jh_ctx *ctx, const jh_history *dh, const jh_long_fork_opts 
         cnt = ctx->ws<int64_t>(WS_LF_CNT, R);
         grp = ctx->ws<long long>(WS_LF_GRP, R);
         mask = ctx->ws<unsigned long long>(WS_LF_MASK, R);
-        k_lf_compact<0><<<g, 256, 0, st>>>(dh->value, dh->value2, n, vec, words_r, base_r, half, row, start, cnt, m);
+        k_lf_compact<0><<<g, 256, 0, st>>>(dh->value, dh->value2, n, vec, sel.words[0], sel.base[0], half, row, start, cnt, m);
         // a bad range was replaced by an empty one: the pass below stays inside aux
         k_lf_reads<<<grid_for(R << logL, 256, 4096), 256, 0, st>>>(dh->aux, row, start, cnt, R, gn, logL, grp, mask, m);
     }
@@ -599,9 +486,9 @@ void long_fork_check(jh_ctx *ctx, const jh_history *dh, const jh_long_fork_opts 
     if (W > 0) {
         wkey = ctx->ws<int64_t>(WS_LF_WKEY, W);
         wrow = ctx->ws<int64_t>(WS_LF_WROW, W);
-        k_lf_compact<1><<<g, 256, 0, st>>>(dh->value, dh->value2, n, vec, words_w, base_w, half, wkey, wrow, nullptr, m);
+        k_lf_compact<1><<<g, 256, 0, st>>>(dh->value, dh->value2, n, vec, sel.words[1], sel.base[1], half, wkey, wrow, nullptr, m);
     }
-    LMeta mh = read_meta(m, st);
+    LMeta mh = fetch(m, st);
     if (mh.bad_range) throw_jh(JH_EINVAL, "long-fork: a read's pair range leaves [0, n_aux / 2) or has a negative count");
     if (mh.unsup)
         throw_jh(JH_EUNSUPPORTED, "long-fork: a read of n keys that are not one aligned group, or that names a key twice");
@@ -627,27 +514,27 @@ void long_fork_check(jh_ctx *ctx, const jh_history *dh, const jh_long_fork_opts 
             k_lf_wkeys<<<grid_for(W, 256, 2048), 256, 0, st>>>(wkey, W, kmin, keys, idx);
             hipcub::DoubleBuffer<unsigned long long> kb(keys, keys + W);
             hipcub::DoubleBuffer<uint32_t> vb(idx, idx + W);
-            sort_pairs(ctx, kb, vb, W, bits_of(width), st);
+            sort_pairs(ctx, WS_LF_TMP, kb, vb, (int)W, bits_of(width), st);
             k_lf_repeat_sorted<<<grid_for(W, 256, 2048), 256, 0, st>>>(kb.Current(), vb.Current(), wrow, W, m);
         }
-        mh = read_meta(m, st);
+        mh = fetch(m, st);
         if (mh.mw_row != NONE) {
             res->valid = JH_UNKNOWN;
             res->cause = JH_CAUSE_MULTIPLE_WRITES;
             res->multiple_row = (int64_t)mh.mw_row;
             HIP_TRY(hipMemcpyAsync(&res->multiple_key, dh->value + mh.mw_row, sizeof(int64_t), hipMemcpyDeviceToHost, st));
             HIP_TRY(hipStreamSynchronize(st));
-            elapsed();
+            res->device_ms = timer.stop();
             return;
         }
     }
-    if (R == 0) { elapsed(); return; }
+    if (R == 0) { res->device_ms = timer.stop(); return; }
     if (mh.ill1_row != NONE) {
         res->valid = JH_UNKNOWN;
         res->cause = JH_CAUSE_ILLEGAL_HISTORY;
         res->illegal_kind = 1;
         res->illegal_row = (int64_t)mh.ill1_row;
-        elapsed();
+        res->device_ms = timer.stop();
         return;
     }
 
@@ -673,15 +560,12 @@ void long_fork_check(jh_ctx *ctx, const jh_history *dh, const jh_long_fork_opts 
         k_lf_gkeys<<<gr, 256, 0, st>>>(grp, R, gmin, keys, idx);
         hipcub::DoubleBuffer<unsigned long long> kb(keys, keys + R);
         hipcub::DoubleBuffer<uint32_t> vb(idx, idx + R);
-        sort_pairs(ctx, kb, vb, R, bits_of(gwidth), st);
+        sort_pairs(ctx, WS_LF_TMP, kb, vb, (int)R, bits_of(gwidth), st);
         k_lf_starts<<<grid_for(R + 1, 256, 2048), 256, 0, st>>>(kb.Current(), R, stf);
-        excl_scan(ctx, stf, rank, R + 1, st);
+        excl_sum(ctx, WS_LF_TMP, as_input(stf), rank, (int)(R + 1), st);
         // the exclusive sum at i + 1 is the inclusive rank of i; at R it is the last rank
         k_lf_scatter<<<gr, 256, 0, st>>>(rank + 1, vb.Current(), R, slot);
-        uint32_t last = 0;
-        HIP_TRY(hipMemcpyAsync(&last, rank + R, sizeof last, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        G = (unsigned long long)last + 1;
+        G = (unsigned long long)fetch(rank + R, st) + 1;
     }
 
     // 4. the chain test
@@ -694,20 +578,20 @@ void long_fork_check(jh_ctx *ctx, const jh_history *dh, const jh_long_fork_opts 
     HIP_TRY(hipMemsetAsync(gbits, 0, sizeof(unsigned) * gw, st));
     k_lf_fill<<<grid_for((int64_t)T, 256, 2048), 256, 0, st>>>((unsigned long long *)vtab, (int64_t)T, (unsigned long long)JH_NIL);
     k_lf_count<<<grid_for(R << logL, 256, 4096), 256, 0, st>>>(dh->aux, start, grp, slot, R, gn, logL, ctab, vtab, m);
-    mh = read_meta(m, st);
+    mh = fetch(m, st);
     if (mh.conflict) {
         k_lf_conflict_row<<<gr, 256, 0, st>>>(dh->aux, row, start, slot, R, gn, ctab, m);
-        mh = read_meta(m, st);
+        mh = fetch(m, st);
         res->valid = JH_UNKNOWN;
         res->cause = JH_CAUSE_ILLEGAL_HISTORY;
         res->illegal_kind = 2;
         res->illegal_row = (int64_t)mh.ill2_row;
-        elapsed();
+        res->device_ms = timer.stop();
         return;
     }
     k_lf_test<<<gr, 256, 0, st>>>(mask, slot, R, (int)gn, ctab, gbits, m);
-    mh = read_meta(m, st);
-    if (!mh.any_fail) { elapsed(); return; }
+    mh = fetch(m, st);
+    if (!mh.any_fail) { res->device_ms = timer.stop(); return; }
 
     // 5. the forks of the flagged groups
     res->valid = JH_INVALID;
@@ -715,19 +599,14 @@ void long_fork_check(jh_ctx *ctx, const jh_history *dh, const jh_long_fork_opts 
     uint8_t *flag = ctx->ws<uint8_t>(WS_LF_FLAG, R);
     uint32_t *sus = ctx->ws<uint32_t>(WS_LF_IDX, 2 * R);
     k_lf_suspect<<<gr, 256, 0, st>>>(slot, R, gbits, flag);
-    {
-        hipcub::CountingInputIterator<uint32_t> ids(0);
-        size_t tb = 0;
-        HIP_TRY(hipcub::DeviceSelect::Flagged(nullptr, tb, ids, flag, sus, &m->n_sel, (int)R, st));
-        HIP_TRY(hipcub::DeviceSelect::Flagged(ctx->ws<char>(WS_LF_TMP, tb), tb, ids, flag, sus, &m->n_sel, (int)R, st));
-    }
-    mh = read_meta(m, st);
+    select_flagged(ctx, WS_LF_TMP, hipcub::CountingInputIterator<uint32_t>(0), flag, sus, &m->n_sel, (int)R, st);
+    mh = fetch(m, st);
     const int64_t S = mh.n_sel;
     uint32_t *skey = ctx->ws<uint32_t>(WS_LF_SKEY, 2 * S);
     const int gsu = grid_for(S, 256, 2048);
     k_lf_suskeys<<<gsu, 256, 0, st>>>(sus, S, slot, skey);
     hipcub::DoubleBuffer<uint32_t> kb(skey, skey + S), vb(sus, sus + R);
-    sort_pairs(ctx, kb, vb, S, bits_of(G), st);
+    sort_pairs(ctx, WS_LF_TMP, kb, vb, (int)S, bits_of(G), st);
     unsigned long long *smask = ctx->ws<unsigned long long>(WS_LF_SMASK, S);
     int64_t *srow = ctx->ws<int64_t>(WS_LF_SROW, S);
     long long *pc = ctx->ws<long long>(WS_LF_PC, 2 * (S + 1));
@@ -736,10 +615,8 @@ void long_fork_check(jh_ctx *ctx, const jh_history *dh, const jh_long_fork_opts 
     HIP_TRY(hipMemsetAsync(pc + S, 0, sizeof(long long), st));
     const int gp = grid_for(S, 4, 8192);
     k_lf_pairs<0><<<gp, 256, 0, st>>>(kb.Current(), smask, srow, S, pc, nullptr, 0, nullptr);
-    excl_scan(ctx, pc, off, S + 1, st);
-    long long total = 0;
-    HIP_TRY(hipMemcpyAsync(&total, off + S, sizeof total, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    excl_sum(ctx, WS_LF_TMP, as_input(pc), off, (int)(S + 1), st);
+    const long long total = fetch(off + S, st);
     res->fork_count = total;
     const int64_t k = forks_out ? std::min<int64_t>(total, fork_cap) : 0;
     if (k > 0) {
@@ -748,5 +625,5 @@ void long_fork_check(jh_ctx *ctx, const jh_history *dh, const jh_long_fork_opts 
         HIP_TRY(hipMemcpyAsync(forks_out, out, sizeof(int64_t) * 2 * k, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
     }
-    elapsed();
+    res->device_ms = timer.stop();
 }

@@ -19,12 +19,9 @@
 // value), one inclusive scan of the +-1 deltas, each value's running count is
 // the scan minus the scan before the value's segment, and the failing row is
 // the minimum row with a negative count.
-#include "jh_internal.h"
-#include <hipcub/hipcub.hpp>
-#include <algorithm>
+#include "jh_prims.h"
 
 namespace {
-constexpr int T_INVOKE = 0, T_OK = 1, T_INFO = 3;
 
 struct QMeta {
     long long vmin, vmax;
@@ -280,8 +277,7 @@ QState q_prepare(jh_ctx *ctx, const jh_history *dh, bool drains, hipStream_t st)
     const int g = grid_for(std::max<int64_t>(n, naux), 256, 2048);
     k_q_scan<<<g, 256, 0, st>>>(dh->type, dh->f, dh->value, dh->value2, n, dh->aux, naux, drains ? 1 : 0, q.parts);
     k_q_scan_fin<<<1, 256, 0, st>>>(q.parts, g, q.m);
-    HIP_TRY(hipMemcpyAsync(&q.mh, q.m, sizeof q.mh, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    q.mh = fetch(q.m, st);
     if (q.mh.crashed_drain) throw_jh(JH_EINVAL, "Not sure how to handle a crashed drain operation");
     if (q.mh.n_drain > 0 && q.mh.max_cnt > 0 && !dh->aux) throw_jh(JH_EINVAL, "drain without an aux element array");
     const bool any = q.mh.vmin <= q.mh.vmax;
@@ -309,21 +305,11 @@ void q_pairs(jh_ctx *ctx, const QState &q, const long long *mult, const uint32_t
     const int64_t k = std::min<int64_t>(npairs, cap);
     if (k <= 0 || !out_host) return;
     uint32_t *pos = ctx->ws<uint32_t>(WS_Q_POS, q.S);
-    size_t tb = 0;
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, flag, pos, (int)q.S, st));
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(ctx->ws<char>(WS_Q_TMP, tb), tb, flag, pos, (int)q.S, st));
+    excl_sum(ctx, WS_Q_TMP, flag, pos, (int)q.S, st);
     int64_t *out = ctx->ws<int64_t>(WS_Q_OUT, 2 * k);
     k_q_emit<<<grid_for(q.S, 256), 256, 0, st>>>(q.S, q.span, q.mh.vmin, mult, flag, pos, k, out);
     HIP_TRY(hipMemcpyAsync(out_host, out, sizeof(int64_t) * 2 * k, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-}
-
-double q_elapsed(jh_ctx *ctx, hipStream_t st) {
-    HIP_TRY(hipEventRecord(ctx->ev[1], st));
-    HIP_TRY(hipEventSynchronize(ctx->ev[1]));
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
-    return ms;
 }
 
 }  // namespace
@@ -332,15 +318,14 @@ void total_queue_check(jh_ctx *ctx, const jh_history *dh, jh_queue_result *res, 
                        int64_t cap, hipStream_t st) {
     memset(res, 0, sizeof *res);
     res->fail_entry = -1;
-    HIP_TRY(hipEventRecord(ctx->ev[0], st));
+    DeviceTimer timer{ctx, st};
+    timer.start();
     QState q = q_prepare(ctx, dh, true, st);
     const int64_t nd = q.mh.n_drain;
     if (nd > 0 && q.mh.max_cnt > 0) {
         int64_t *dr = ctx->ws<int64_t>(WS_Q_ROWS, nd + 1);
         hipcub::CountingInputIterator<int64_t> rows(0);
-        size_t tb = 0;
-        HIP_TRY(hipcub::DeviceSelect::Flagged(nullptr, tb, rows, q.flag, dr, dr + nd, dh->n, st));
-        HIP_TRY(hipcub::DeviceSelect::Flagged(ctx->ws<char>(WS_Q_TMP, tb), tb, rows, q.flag, dr, dr + nd, dh->n, st));
+        select_flagged(ctx, WS_Q_TMP, rows, q.flag, dr, dr + nd, dh->n, st);
         const unsigned gx = (unsigned)((q.mh.max_cnt + DRAIN_CHUNK - 1) / DRAIN_CHUNK);
         for (int64_t r0 = 0; r0 < nd; r0 += 65535)
             k_q_drain<<<dim3(gx, (unsigned)std::min<int64_t>(65535, nd - r0)), 256, 0, st>>>(
@@ -351,8 +336,7 @@ void total_queue_check(jh_ctx *ctx, const jh_history *dh, jh_queue_result *res, 
     const int g = grid_for(q.S, 256, 2048);
     k_q_total<<<g, 256, 0, st>>>(q.S, q.a, q.e, q.d, mult, flag, q.parts);
     k_q_total_fin<<<1, 256, 0, st>>>(q.parts, g, q.m);
-    HIP_TRY(hipMemcpyAsync(&q.mh, q.m, sizeof q.mh, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    q.mh = fetch(q.m, st);
     res->attempt_count = q.mh.cnt[0]; res->acknowledged_count = q.mh.cnt[1]; res->ok_count = q.mh.cnt[2];
     res->unexpected_count = q.mh.cnt[3]; res->duplicated_count = q.mh.cnt[4];
     res->lost_count = q.mh.cnt[5]; res->recovered_count = q.mh.cnt[6];
@@ -361,49 +345,38 @@ void total_queue_check(jh_ctx *ctx, const jh_history *dh, jh_queue_result *res, 
         res->n_pairs[s] = q.mh.npairs[s];
         q_pairs(ctx, q, mult + s * q.S, flag + s * q.S, q.mh.npairs[s], cap, outs[s], st);
     }
-    res->device_ms = q_elapsed(ctx, st);
+    res->device_ms = timer.stop();
 }
 
 void queue_check(jh_ctx *ctx, const jh_history *dh, jh_queue_result *res, int64_t *final_out, int64_t cap,
                  hipStream_t st) {
     memset(res, 0, sizeof *res);
     res->fail_entry = -1;
-    HIP_TRY(hipEventRecord(ctx->ev[0], st));
+    DeviceTimer timer{ctx, st};
+    timer.start();
     QState q = q_prepare(ctx, dh, false, st);
     const int64_t k = q.mh.n_sel;
     if (k > 0) {
         int64_t *rb = ctx->ws<int64_t>(WS_Q_ROWS, 2 * k + 1);
         int64_t *rows_sel = rb, *rows_sorted = rb + k;
         hipcub::CountingInputIterator<int64_t> rows(0);
-        size_t tb = 0;
-        HIP_TRY(hipcub::DeviceSelect::Flagged(nullptr, tb, rows, q.flag, rows_sel, rb + 2 * k, dh->n, st));
-        HIP_TRY(hipcub::DeviceSelect::Flagged(ctx->ws<char>(WS_Q_TMP, tb), tb, rows, q.flag, rows_sel, rb + 2 * k,
-                                              dh->n, st));
+        select_flagged(ctx, WS_Q_TMP, rows, q.flag, rows_sel, rb + 2 * k, dh->n, st);
         uint32_t *kb = ctx->ws<uint32_t>(WS_Q_KEYS, 2 * k + q.S);
         uint32_t *keys = kb, *keys_sorted = kb + k, *seg_off = kb + 2 * k;
         k_q_keys<<<grid_for(k, 256), 256, 0, st>>>(dh->value, rows_sel, k, q.mh.vmin, q.span, keys);
         int end_bit = 1;
         while (end_bit < 32 && (1LL << end_bit) < q.S) end_bit++;
-        tb = 0;
-        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, keys, keys_sorted, rows_sel, rows_sorted, k, 0,
-                                                   end_bit, st));
-        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(ctx->ws<char>(WS_Q_TMP, tb), tb, keys, keys_sorted, rows_sel,
-                                                   rows_sorted, k, 0, end_bit, st));
+        sort_pairs(ctx, WS_Q_TMP, keys, keys_sorted, rows_sel, rows_sorted, k, end_bit, st);
         // segment start of each value = exclusive scan of its row count (a + d)
         long long *db = ctx->ws<long long>(WS_Q_MULT, 2 * k);
         long long *delta = db, *scan = db + k;
         k_q_delta<<<grid_for(k, 256), 256, 0, st>>>(dh->f, rows_sorted, k, delta);
-        tb = 0;
-        HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, tb, delta, scan, k, st));
-        HIP_TRY(hipcub::DeviceScan::InclusiveSum(ctx->ws<char>(WS_Q_TMP, tb), tb, delta, scan, k, st));
+        incl_sum(ctx, WS_Q_TMP, delta, scan, k, st);
         uint32_t *cnt = ctx->ws<uint32_t>(WS_Q_POS, q.S);
         k_q_segcount<<<grid_for(q.S, 256), 256, 0, st>>>(q.S, q.a, q.d, cnt);
-        tb = 0;
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, cnt, seg_off, (int)q.S, st));
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(ctx->ws<char>(WS_Q_TMP, tb), tb, cnt, seg_off, (int)q.S, st));
+        excl_sum(ctx, WS_Q_TMP, cnt, seg_off, (int)q.S, st);
         k_q_neg<<<grid_for(k, 256, 2048), 256, 0, st>>>(keys_sorted, rows_sorted, delta, scan, seg_off, k, q.m);
-        HIP_TRY(hipMemcpyAsync(&q.mh, q.m, sizeof q.mh, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
+        q.mh = fetch(q.m, st);
     }
     if (k > 0 && q.mh.fail_row != ~0ULL) {
         res->valid = JH_INVALID;
@@ -418,10 +391,9 @@ void queue_check(jh_ctx *ctx, const jh_history *dh, jh_queue_result *res, int64_
         const int g = grid_for(q.S, 256, 2048);
         k_q_final<<<g, 256, 0, st>>>(q.S, q.a, q.d, mult, flag, q.parts);
         k_q_final_fin<<<1, 256, 0, st>>>(q.parts, g, q.m);
-        HIP_TRY(hipMemcpyAsync(&q.mh, q.m, sizeof q.mh, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
+        q.mh = fetch(q.m, st);
         res->n_pairs[0] = q.mh.npairs[0];
         q_pairs(ctx, q, mult, flag, q.mh.npairs[0], cap, final_out, st);
     }
-    res->device_ms = q_elapsed(ctx, st);
+    res->device_ms = timer.stop();
 }

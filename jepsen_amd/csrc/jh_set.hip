@@ -12,11 +12,9 @@
 // Elements live in [vmin, vmax]; each of the three sets is a bitmap over that
 // span (atomicOr of 32-bit words), every set operation is a word-wise
 // boolean, and runs fall out of the bit boundaries of each word.
-#include "jh_internal.h"
-#include <hipcub/hipcub.hpp>
+#include "jh_prims.h"
 
 namespace {
-constexpr int T_INVOKE = 0, T_OK = 1;
 
 struct SetMeta {
     long long vmin, vmax;
@@ -25,14 +23,6 @@ struct SetMeta {
     long long cnt[10];         // attempt, ack, ok, lost, recovered, unexpected; runs of ok, lost, unexpected, recovered
     unsigned long long first_lost_row;
 };
-
-// Row pairs: both rows in one 16-byte load when the columns are 16-byte
-// aligned (vec; workspace and torch allocations are), two 8-byte loads
-// otherwise; a trailing odd row is the last pair's first half
-__device__ __forceinline__ longlong2 ld_pair(const int64_t *__restrict__ c, int64_t i, int64_t n, bool vec) {
-    if (2 * i + 1 < n) return vec ? ((const longlong2 *)c)[i] : make_longlong2(c[2 * i], c[2 * i + 1]);
-    return make_longlong2(c[2 * i], 0);
-}
 
 #ifndef JH_SCAN_GRID
 #define JH_SCAN_GRID 8192     // grid caps of the scan and the byte-map pass (profiles/r04/c2_spill/r4sgrid_*: scan 2048 / 4096 / 8192 / 16384 blocks 493 / 483-501 / 456-458 / 509-516 us)
@@ -620,8 +610,7 @@ static bool set_bitmaps(jh_ctx *ctx, const jh_history *dh, jh_set_result *res, S
     const int vec = ((uintptr_t)dh->type | (uintptr_t)dh->f | (uintptr_t)dh->value) % 16 == 0;
     uint16_t *code = JH_SET_CODE ? ctx->ws<uint16_t>(WS_S_CODE, (size_t)(n + 1) / 2 + 16) : nullptr;   // + a 16-byte tail
     if (n > 0) k_set_scan<<<grid_for((n + 1) / 2, 256, JH_SCAN_GRID), 256, 0, st>>>(dh->type, dh->f, dh->value, n, vec, m, code);
-    HIP_TRY(hipMemcpyAsync(&mh, m, sizeof mh, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    mh = fetch(m, st);
     res->final_read_entry = mh.final_row;
     if (mh.final_row < 0) { res->valid = JH_UNKNOWN; res->cause = JH_CAUSE_NIL_VALUE; return false; }
     int64_t rd[2];
@@ -635,8 +624,7 @@ static bool set_bitmaps(jh_ctx *ctx, const jh_history *dh, jh_set_result *res, S
     const int64_t off = rd[0], cnt = rd[1];
     if (cnt > 0)
         k_set_range<<<grid_for(cnt / 2 + 1, 256, 4096), 256, 0, st>>>(dh->aux, off, cnt, (uintptr_t)dh->aux % 16 == 0, m);
-    HIP_TRY(hipMemcpyAsync(&mh, m, sizeof mh, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    mh = fetch(m, st);
     vmin = mh.vmin;
     long long vmax = mh.vmax;
     if (vmin > vmax) { vmin = 0; vmax = 0; }
@@ -660,9 +648,7 @@ static bool set_bitmaps(jh_ctx *ctx, const jh_history *dh, jh_set_result *res, S
             uint32_t *rin = ctx->ws<uint32_t>(WS_S_RB_OUT, cnt);
             const int64_t *e = dh->aux + off;
             k_rb_hist<<<nblk, 256, nbins * 4, st>>>(e, cnt, vmin, sb, nbins, nblk, hist);
-            size_t tb = 0;
-            HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, hist, pos, (int)nh, st));
-            HIP_TRY(hipcub::DeviceScan::ExclusiveSum(ctx->ws<char>(WS_S_TMP, tb), tb, hist, pos, (int)nh, st));
+            excl_sum(ctx, WS_S_TMP, hist, pos, (int)nh, st);
             const int sc_lds = nbins * 12 + RB_CH * 6;
             HIP_TRY(hipFuncSetAttribute((const void *)k_rb_scatter, hipFuncAttributeMaxDynamicSharedMemorySize, sc_lds));
             k_rb_scatter<<<nblk, 256, sc_lds, st>>>(e, cnt, vmin, sb, nbins, nblk, hist, pos, rin);
@@ -711,16 +697,15 @@ void set_check(jh_ctx *ctx, const jh_history *dh, jh_set_result *res, int64_t *r
     uint32_t *starts = ctx->ws<uint32_t>(WS_S_RUNS, 8 * nw + 8);
     uint32_t *spos = starts + 4 * nw;
     k_set_count<<<grid_for(nw, 256, 2048), 256, 0, st>>>(A, D, R, nw, starts, nullptr, m);
-    size_t tb = 0;
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, starts, spos, (int)nw, st));
+    int set = 0;                  // per-set run numbering starts at 0: four scans of one size over one scratch buffer
+    auto scan = JH_CUB(DeviceScan::ExclusiveSum, starts + set * nw, spos + set * nw, (int)nw, st);
+    size_t tb = cub_size(scan);
     void *tmp = ctx->ws<char>(WS_S_TMP, tb);
-    for (int s = 0; s < 4; s++)   // per-set run numbering starts at 0
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp, tb, starts + s * nw, spos + s * nw, (int)nw, st));
+    for (set = 0; set < 4; set++) HIP_TRY(scan(tmp, tb));
     const int64_t cap = runs_cap;
     int64_t *runs = ctx->ws<int64_t>(WS_C_OUT, 8 * std::max<int64_t>(cap, 1));
     k_set_emit<<<grid_for(nw, 256), 256, 0, st>>>(A, D, R, nw, vmin, spos, runs, cap);
-    HIP_TRY(hipMemcpyAsync(&mh, m, sizeof mh, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    mh = fetch(m, st);
     set_finish(res, mh);
     for (int s = 0; s < 4; s++) {
         const int64_t k = std::min<int64_t>(res->n_runs[s], cap);

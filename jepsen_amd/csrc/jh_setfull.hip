@@ -22,12 +22,9 @@
 //   6. k_sf_final       set-full-element-results (:289-345) per element
 //   7. selects and radix sorts: lost / never-read / stale lists (sorted), the
 //      latency quantiles (frequency-distribution, :347-358) and worst-stale.
-#include "jh_internal.h"
-#include <hipcub/hipcub.hpp>
-#include <algorithm>
+#include "jh_prims.h"
 
 namespace {
-constexpr int T_INVOKE = 0, T_OK = 1;
 
 struct SfMeta {
     long long vmin, vmax;
@@ -389,8 +386,8 @@ void set_full_check(jh_ctx *ctx, const jh_history *dh, const int64_t *time_dev, 
                     jh_set_full_result *res, int64_t *lists_out[3], int64_t list_cap, hipStream_t st) {
     memset(res, 0, sizeof *res);
     const int64_t n = dh->n;
-    hipEvent_t e0 = ctx->ev[0], e1 = ctx->ev[1];
-    HIP_TRY(hipEventRecord(e0, st));
+    DeviceTimer timer{ctx, st};
+    timer.start();
     SfMeta *m = ctx->ws<SfMeta>(WS_SF_META, 1);
     SfMeta mh{};
     mh.vmin = LLONG_MAX; mh.vmax = LLONG_MIN;
@@ -401,8 +398,7 @@ void set_full_check(jh_ctx *ctx, const jh_history *dh, const int64_t *time_dev, 
         k_sf_scan<<<g, 256, 0, st>>>(dh->process, dh->type, dh->f, dh->value, dh->value2, n, parts);
         k_sf_scan_fin<<<1, 256, 0, st>>>(parts, g, m);
     }
-    HIP_TRY(hipMemcpyAsync(&mh, m, sizeof mh, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    mh = fetch(m, st);
     if (mh.nil_elem) throw_jh(JH_EUNSUPPORTED, "nil set-full element");
     if (mh.n_reads > 0 && mh.read_elems > 0 && !dh->aux) throw_jh(JH_EINVAL, "set read without an aux element array");
     res->n_reads = mh.n_reads;
@@ -416,11 +412,7 @@ void set_full_check(jh_ctx *ctx, const jh_history *dh, const int64_t *time_dev, 
         else if (res->stable_count == 0) res->valid = JH_UNKNOWN;
         else if (linearizable && res->stale_count > 0) res->valid = JH_INVALID;
         else res->valid = JH_VALID;
-        HIP_TRY(hipEventRecord(e1, st));
-        HIP_TRY(hipEventSynchronize(e1));
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-        res->device_ms = ms;
+        res->device_ms = timer.stop();
     };
     if (mh.n_inv == 0) { finish(0); return; }
     const unsigned long long span = (unsigned long long)(mh.vmax - mh.vmin) + 1;
@@ -433,14 +425,11 @@ void set_full_check(jh_ctx *ctx, const jh_history *dh, const int64_t *time_dev, 
     int32_t *lut = ctx->ws<int32_t>(WS_SF_LUT, span);
     HIP_TRY(hipMemsetAsync(flag, 0, sizeof(uint32_t) * span, st));
     k_sf_mark<<<grid_for(n, 256), 256, 0, st>>>(dh->process, dh->type, dh->f, dh->value, n, vmin, flag);
-    size_t tb = 0;
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, flag, (uint32_t *)lut, (int64_t)span, st));
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(ctx->ws<char>(WS_SF_TMP, tb), tb, flag, (uint32_t *)lut, (int64_t)span, st));
+    excl_sum(ctx, WS_SF_TMP, flag, (uint32_t *)lut, (int64_t)span, st);
     const int64_t cap_elem = mh.n_inv;                      // >= distinct elements
     int64_t *elem = ctx->ws<int64_t>(WS_SF_ELEM, cap_elem);
     k_sf_lut<<<grid_for(span, 256), 256, 0, st>>>(flag, lut, span, vmin, elem, m);
-    HIP_TRY(hipMemcpyAsync(&mh, m, sizeof mh, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    mh = fetch(m, st);
     const int64_t M = mh.n_elem;
 
     // 3. per-element state; 0xff bytes = -1 (signed) / none (unsigned)
@@ -459,9 +448,7 @@ void set_full_check(jh_ctx *ctx, const jh_history *dh, const int64_t *time_dev, 
         int64_t *rr = ctx->ws<int64_t>(WS_SF_READS, 2 * R + 1);
         int64_t *rrow = rr, *rinv = rr + R, *nsel = rr + 2 * R;
         hipcub::CountingInputIterator<int64_t> rows(0);
-        tb = 0;
-        HIP_TRY(hipcub::DeviceSelect::Flagged(nullptr, tb, rows, rflag, rrow, nsel, n, st));
-        HIP_TRY(hipcub::DeviceSelect::Flagged(ctx->ws<char>(WS_SF_TMP, tb), tb, rows, rflag, rrow, nsel, n, st));
+        select_flagged(ctx, WS_SF_TMP, rows, rflag, rrow, nsel, n, st);
         k_sf_inv<<<(unsigned)((R + 3) / 4), 256, 0, st>>>(dh->process, dh->type, dh->f, rrow, R, rinv, m);
         // (a bad read is reported after the outcomes' sync: the kernels below tolerate rinv = -1)
 
@@ -494,8 +481,7 @@ void set_full_check(jh_ctx *ctx, const jh_history *dh, const int64_t *time_dev, 
                                       f_stable, f_lost, f_never, f_stale, parts);
         k_sf_final_fin<<<1, 256, 0, st>>>(parts, g, m);
     }
-    HIP_TRY(hipMemcpyAsync(&mh, m, sizeof mh, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    mh = fetch(m, st);
 
     if (mh.bad_read) throw_jh(JH_EINVAL, "an :ok :read without a read invocation before it");
 
@@ -505,11 +491,7 @@ void set_full_check(jh_ctx *ctx, const jh_history *dh, const int64_t *time_dev, 
     int64_t *lst[3] = {sel, sel + M, sel + 2 * M};
     int64_t *a0 = sel + 3 * M, *a1 = sel + 4 * M, *a2 = sel + 5 * M, *a3 = sel + 6 * M, *ns = sel + 7 * M;
     SfOut *dout = (SfOut *)(ns + 8);
-    auto select = [&](auto in, const uint8_t *flg, auto *out) {
-        size_t t = 0;
-        HIP_TRY(hipcub::DeviceSelect::Flagged(nullptr, t, in, flg, out, ns, M, st));
-        HIP_TRY(hipcub::DeviceSelect::Flagged(ctx->ws<char>(WS_SF_TMP, t), t, in, flg, out, ns, M, st));
-    };
+    auto select = [&](auto in, const uint8_t *flg, auto *out) { select_flagged(ctx, WS_SF_TMP, in, flg, out, ns, M, st); };
     const int64_t counts[3] = {mh.cnt[1], mh.cnt[2], mh.cnt[3]};
     const uint8_t *lflags[3] = {f_lost, f_never, f_stale};
     for (int s = 0; s < 3; s++)
@@ -517,10 +499,7 @@ void set_full_check(jh_ctx *ctx, const jh_history *dh, const int64_t *time_dev, 
     const double points[JH_SF_QUANTILES] = {0, 0.5, 0.95, 0.99, 1};
     auto quantiles = [&](const long long *lat, const uint8_t *flg, int64_t c, int which) {
         select(lat, flg, (long long *)a0);
-        size_t t = 0;
-        HIP_TRY(hipcub::DeviceRadixSort::SortKeys(nullptr, t, (long long *)a0, (long long *)a1, c, 0, 64, st));
-        HIP_TRY(hipcub::DeviceRadixSort::SortKeys(ctx->ws<char>(WS_SF_TMP, t), t, (long long *)a0, (long long *)a1,
-                                                  c, 0, 64, st));
+        sort_keys(ctx, WS_SF_TMP, (long long *)a0, (long long *)a1, c, 64, st);
         Pick5 pk;
         for (int i = 0; i < JH_SF_QUANTILES; i++)            // frequency-distribution, checker.clj:347-358
             pk.idx[i] = std::min<int64_t>(c - 1, (int64_t)std::floor((double)c * points[i]));
@@ -532,11 +511,7 @@ void set_full_check(jh_ctx *ctx, const jh_history *dh, const int64_t *time_dev, 
         const int64_t S = mh.cnt[3];
         select(slat, f_stale, (long long *)a0);
         select(hipcub::CountingInputIterator<int32_t>(0), f_stale, (int32_t *)a1);
-        size_t t = 0;
-        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, t, (long long *)a0, (long long *)a2, (int32_t *)a1,
-                                                   (int32_t *)a3, S, 0, 64, st));
-        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(ctx->ws<char>(WS_SF_TMP, t), t, (long long *)a0, (long long *)a2,
-                                                   (int32_t *)a1, (int32_t *)a3, S, 0, 64, st));
+        sort_pairs(ctx, WS_SF_TMP, (long long *)a0, (long long *)a2, (int32_t *)a1, (int32_t *)a3, S, 64, st);
         res->n_worst = (int)std::min<int64_t>(S, JH_SF_WORST);
         k_sf_worst<<<1, 64, 0, st>>>((long long *)a2, (int32_t *)a3, S, (int)res->n_worst, elem, known, la,
                                      dout->worst);

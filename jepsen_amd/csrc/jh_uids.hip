@@ -27,12 +27,9 @@
 //                      reference's (sort-by val) / reverse / (take 48)
 // nil is never marked or sorted: it is a duplicated id with count nil_count
 // when nil_count >= 2, and takes part in the selection as the smallest id.
-#include "jh_internal.h"
-#include <hipcub/hipcub.hpp>
-#include <algorithm>
+#include "jh_prims.h"
 
 namespace {
-constexpr int T_INVOKE = 0, T_OK = 1;
 constexpr int U_PAIRS = 8;                  // row pairs per thread per tile
 constexpr int U_TILE = 256 * U_PAIRS;       // row pairs per tile (4096 rows)
 
@@ -44,11 +41,6 @@ struct UMeta {
     unsigned long long n_runs;          // duplicated non-nil ids
     int n_sel[2];                       // DeviceSelect counts (starts, ends)
 };
-
-__device__ __forceinline__ longlong2 u_ld_pair(const int64_t *__restrict__ c, int64_t i, int64_t n, bool vec) {
-    if (2 * i + 1 < n) return vec ? ((const longlong2 *)c)[i] : make_longlong2(c[2 * i], c[2 * i + 1]);
-    return make_longlong2(c[2 * i], 0);
-}
 
 // One tile = 256 threads x U_PAIRS row pairs, pair p0 + u * 256 + thread, so
 // every wave-instruction loads 1 KiB. The tile's non-nil acked ids go to the
@@ -73,7 +65,7 @@ __global__ void __launch_bounds__(256) k_uid_scan(const int64_t *__restrict__ ty
         for (int u = 0; u < U_PAIRS; u++) {
             const int64_t p = p0 + u * 256;
             if (p < np) {
-                t2[u] = u_ld_pair(type, p, n, vec); f2[u] = u_ld_pair(f, p, n, vec); v2[u] = u_ld_pair(value, p, n, vec);
+                t2[u] = ld_pair(type, p, n, vec); f2[u] = ld_pair(f, p, n, vec); v2[u] = ld_pair(value, p, n, vec);
             } else {
                 t2[u] = make_longlong2(-1, -1); f2[u] = t2[u]; v2[u] = t2[u];
             }
@@ -268,20 +260,11 @@ int bits_of(unsigned long long x) {
 }
 
 // sorts cnt keys; returns the sorted array (keys or alt)
-unsigned long long *sort_keys(jh_ctx *ctx, unsigned long long *keys, unsigned long long *alt, int64_t cnt, int end_bit,
+unsigned long long *sorted_keys(jh_ctx *ctx, unsigned long long *keys, unsigned long long *alt, int64_t cnt, int end_bit,
                               hipStream_t st) {
     hipcub::DoubleBuffer<unsigned long long> db(keys, alt);
-    size_t tb = 0;
-    HIP_TRY(hipcub::DeviceRadixSort::SortKeys(nullptr, tb, db, (int)cnt, 0, end_bit, st));
-    HIP_TRY(hipcub::DeviceRadixSort::SortKeys(ctx->ws<char>(WS_U_TMP, tb), tb, db, (int)cnt, 0, end_bit, st));
+    sort_keys(ctx, WS_U_TMP, db, (int)cnt, end_bit, st);
     return db.Current();
-}
-
-UMeta read_meta(const UMeta *m, hipStream_t st) {
-    UMeta h;
-    HIP_TRY(hipMemcpyAsync(&h, m, sizeof h, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return h;
 }
 
 }  // namespace
@@ -293,14 +276,8 @@ void unique_ids_check(jh_ctx *ctx, const jh_history *dh, const jh_unique_ids_opt
     res->range_lo = res->range_hi = JH_NIL;
     const int64_t n = dh->n;
     if (n == 0) return;
-    HIP_TRY(hipEventRecord(ctx->ev[0], st));
-    auto elapsed = [&] {
-        HIP_TRY(hipEventRecord(ctx->ev[1], st));
-        HIP_TRY(hipEventSynchronize(ctx->ev[1]));
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
-        res->device_ms = ms;
-    };
+    DeviceTimer timer{ctx, st};
+    timer.start();
     UMeta *m = ctx->ws<UMeta>(WS_U_META, 1);
     long long *parts = ctx->ws<long long>(WS_U_PART, 4 * 2048);
     int64_t *list = ctx->ws<int64_t>(WS_U_LIST, n);           // every row may be an ack
@@ -310,7 +287,7 @@ void unique_ids_check(jh_ctx *ctx, const jh_history *dh, const jh_unique_ids_opt
     const int g = grid_for(n_tiles, 1, 2048);
     k_uid_scan<<<g, 256, 0, st>>>(dh->type, dh->f, dh->value, n, opts->f_generate, vec, list, m, parts);
     k_uid_scan_fin<<<1, 256, 0, st>>>(parts, g, m);
-    UMeta mh = read_meta(m, st);
+    UMeta mh = fetch(m, st);
     const int64_t k = (int64_t)mh.n_list;
     const unsigned long long n_ack = mh.n_list + (unsigned long long)mh.nil_count;
     if (n_ack > 0x7fffffffULL) throw_jh(JH_EUNSUPPORTED, "more than 2^31 - 1 acknowledged ids");
@@ -319,7 +296,7 @@ void unique_ids_check(jh_ctx *ctx, const jh_history *dh, const jh_unique_ids_opt
     res->nil_count = mh.nil_count;
     const int has_nil = mh.nil_count >= 2;
     if (k > 0) { res->range_lo = mh.nil_count > 0 ? JH_NIL : mh.lo; res->range_hi = mh.hi; }
-    if (n_ack == 0) { elapsed(); return; }
+    if (n_ack == 0) { res->device_ms = timer.stop(); return; }
 
     const unsigned long long lo = (unsigned long long)mh.lo;
     const unsigned long long width = k > 0 ? (unsigned long long)mh.hi - lo : 0;   // span - 1: cannot wrap
@@ -338,18 +315,18 @@ void unique_ids_check(jh_ctx *ctx, const jh_history *dh, const jh_unique_ids_opt
         unsigned long long *extra = ctx->ws<unsigned long long>(WS_U_ALT, k);
         HIP_TRY(hipMemsetAsync(bits, 0, sizeof(unsigned long long) * nw, st));
         k_uid_mark<<<grid_for(k, 256, 2048), 256, 0, st>>>(list, k, lo, bits, extra, m);
-        mh = read_meta(m, st);
+        mh = fetch(m, st);
         n_sorted = (int64_t)mh.n_extra;
         each = 1;
         if (n_sorted > 0) {
             unsigned long long *alt = ctx->ws<unsigned long long>(WS_U_ALT2, n_sorted);
-            sorted = sort_keys(ctx, extra, alt, n_sorted, bits_of(width), st);
+            sorted = sorted_keys(ctx, extra, alt, n_sorted, bits_of(width), st);
         }
     } else if (k > 0) {
         unsigned long long *keys = (unsigned long long *)list;
         unsigned long long *alt = ctx->ws<unsigned long long>(WS_U_ALT, k);
         k_uid_keys<<<grid_for(k, 256, 2048), 256, 0, st>>>(keys, k, lo);
-        sorted = sort_keys(ctx, keys, alt, k, bits_of(width), st);
+        sorted = sorted_keys(ctx, keys, alt, k, bits_of(width), st);
         n_sorted = k;
     }
 
@@ -358,7 +335,7 @@ void unique_ids_check(jh_ctx *ctx, const jh_history *dh, const jh_unique_ids_opt
     if (n_sorted > 0) {
         flag = ctx->ws<uint8_t>(WS_U_FLAG, n_sorted);
         k_uid_runs<<<grid_for(n_sorted, 256, 2048), 256, 0, st>>>(sorted, n_sorted, each, flag, m);
-        mh = read_meta(m, st);
+        mh = fetch(m, st);
         n_runs = (int64_t)mh.n_runs;
     }
     const int64_t D = n_runs + has_nil;
@@ -371,13 +348,13 @@ void unique_ids_check(jh_ctx *ctx, const jh_history *dh, const jh_unique_ids_opt
         if (n_runs > 0) {
             hipcub::CountingInputIterator<int64_t> rows(0);
             hipcub::TransformInputIterator<uint8_t, FlagBit, const uint8_t *> f0(flag, FlagBit{0}), f1(flag, FlagBit{1});
-            size_t tb = 0, tb1 = 0;
-            HIP_TRY(hipcub::DeviceSelect::Flagged(nullptr, tb, rows, f0, starts, m->n_sel, (int)n_sorted, st));
-            HIP_TRY(hipcub::DeviceSelect::Flagged(nullptr, tb1, rows, f1, ends, m->n_sel + 1, (int)n_sorted, st));
-            tb = std::max(tb, tb1);
+            // one scratch buffer of the larger size for both calls
+            auto sel_starts = JH_CUB(DeviceSelect::Flagged, rows, f0, starts, m->n_sel, (int)n_sorted, st);
+            auto sel_ends = JH_CUB(DeviceSelect::Flagged, rows, f1, ends, m->n_sel + 1, (int)n_sorted, st);
+            size_t tb = std::max(cub_size(sel_starts), cub_size(sel_ends));
             char *tmp = ctx->ws<char>(WS_U_TMP, tb);
-            HIP_TRY(hipcub::DeviceSelect::Flagged(tmp, tb, rows, f0, starts, m->n_sel, (int)n_sorted, st));
-            HIP_TRY(hipcub::DeviceSelect::Flagged(tmp, tb, rows, f1, ends, m->n_sel + 1, (int)n_sorted, st));
+            HIP_TRY(sel_starts(tmp, tb));
+            HIP_TRY(sel_ends(tmp, tb));
         }
         int64_t *pairs = ctx->ws<int64_t>(WS_U_PAIRS, 2 * D);
         unsigned long long *cnt = ctx->ws<unsigned long long>(WS_U_CNT, 2 * D);
@@ -391,18 +368,16 @@ void unique_ids_check(jh_ctx *ctx, const jh_history *dh, const jh_unique_ids_opt
             // ascending id (the positions are the id order)
             unsigned long long max_c = (unsigned long long)std::max<long long>(mh.nil_count, 2);
             max_c = std::max<unsigned long long>(max_c, (unsigned long long)n_sorted + 1);
-            size_t tb = 0, tb1 = 0;
-            HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, cnt, cnt + D, idx, idx + D, (int)D, 0,
-                                                       bits_of(max_c), st));
+            // one scratch buffer of the larger size for both sorts
+            auto by_count = JH_CUB(DeviceRadixSort::SortPairs, cnt, cnt + D, idx, idx + D, (int)D, 0, bits_of(max_c), st);
+            size_t tb = cub_size(by_count);
             uint32_t *sel = ctx->ws<uint32_t>(WS_U_SEL, out_k);
-            HIP_TRY(hipcub::DeviceRadixSort::SortKeys(nullptr, tb1, idx + D + (D - out_k), sel, (int)out_k, 0,
-                                                      bits_of((unsigned long long)D), st));
-            tb = std::max(tb, tb1);
+            auto by_id = JH_CUB(DeviceRadixSort::SortKeys, idx + D + (D - out_k), sel, (int)out_k, 0,
+                                bits_of((unsigned long long)D), st);
+            tb = std::max(tb, cub_size(by_id));
             char *tmp = ctx->ws<char>(WS_U_TMP, tb);
-            HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, tb, cnt, cnt + D, idx, idx + D, (int)D, 0,
-                                                       bits_of(max_c), st));
-            HIP_TRY(hipcub::DeviceRadixSort::SortKeys(tmp, tb, idx + D + (D - out_k), sel, (int)out_k, 0,
-                                                      bits_of((unsigned long long)D), st));
+            HIP_TRY(by_count(tmp, tb));
+            HIP_TRY(by_id(tmp, tb));
             int64_t *out = ctx->ws<int64_t>(WS_U_OUT, 2 * out_k);
             k_uid_gather<<<grid_for(out_k, 256, 2048), 256, 0, st>>>(pairs, sel, out_k, out);
             src = out;
@@ -410,5 +385,5 @@ void unique_ids_check(jh_ctx *ctx, const jh_history *dh, const jh_unique_ids_opt
         HIP_TRY(hipMemcpyAsync(dup_out, src, sizeof(int64_t) * 2 * out_k, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
     }
-    elapsed();
+    res->device_ms = timer.stop();
 }

@@ -18,7 +18,7 @@ from jepsen_amd import _abi as A
 from jepsen_amd import _native, checker, independent, synth
 from jepsen_amd import causal_reverse as CR
 from jepsen_amd.history import Columns, tuple_
-from causal_reverse_cases import CASES, I64_MAX, I64_MIN, QUIRK_AS_SETS, edge, rd, seq, wi, wo
+from causal_reverse_cases import CASES, I64_MAX, I64_MIN, QUIRK_AS_SETS, edge, rd, ri, seq, wi, wo
 from causal_reverse_ref import RAW_FIELDS, clj_check, ref_cols
 
 pytestmark = pytest.mark.gpu
@@ -124,6 +124,40 @@ def test_bitmap_and_wave_edges(ctx, c):
         assert want["errors"][:, 2:4].tolist() == [[c, 1], [c, 1]] and want["missing"].tolist() == [100 + drop] * 2
         assert want["entries"] == 3 * c + 2
         maps_agree(h)
+
+
+def tile_edge_history(N):
+    """N rows of one key. Around the first tile edge E = CR_TILE: a write and an
+    :ok read on E - 2 and E - 1, a write and an :ok read on E and E + 1. 3 is
+    invoked (E - 2) after 1 and 2 completed, so the read of [3] alone on E + 1
+    misses both; the reads on E - 1 and E + 2 are satisfied. A history that
+    goes on past the edge ends with the violating read once more."""
+    E = A.CR_TILE
+    h = [ri() for _ in range(N)]
+    h[:4] = seq(1, 2)
+    for i, o in ((E - 2, wi(3)), (E - 1, rd([2, 1])), (E, wo(3)), (E + 1, rd([3])), (E + 2, rd([1, 3, 2]))):
+        if i < N:
+            h[i] = o
+    if N > E + 5:
+        h[N - 1] = rd([3])
+    return h
+
+
+@pytest.mark.parametrize("d", [-1, 0, 1])
+def test_tile_edges(ctx, d):
+    """CR_TILE - 1, CR_TILE and CR_TILE + 1 rows (then two tiles more): the
+    flagged rows on both sides of a tile edge, and a last tile of one row, of a
+    full tile and of a full tile less one row."""
+    for extra in (0, 2 * A.CR_TILE):
+        N = A.CR_TILE + d + extra
+        cols = CR.encode(tile_edge_history(N))
+        assert cols.n == N
+        for path in PATHS:                                   # the CPU reference takes the history, before any device run
+            assert ref_cols(cols, path)["rc"] == A.JH_OK
+        want = agree(ctx, cols)
+        bad = [i for i in (A.CR_TILE + 1, N - 1) if extra and i < N]
+        assert want["errors"][:, 0].tolist() == bad and want["missing"].tolist() == [1, 2] * len(bad)
+        assert want["read_count"] == sum(1 for i in (A.CR_TILE - 1, A.CR_TILE + 1, A.CR_TILE + 2) if i < N) + bool(extra)
 
 
 def big_key(n_values):

@@ -172,23 +172,51 @@ def test_read_counts(ctx, k):
     assert want["fork_count"] == sum(1 for i in range(k) if masks[(4 * i) // k] in (0b010, 0b011))
 
 
+def tile_edge_items(N):
+    """N rows with a group whose reads straddle the first tile edge and a write
+    on each side of it."""
+    items = [("x",) if i % 3 else ("i",) for i in range(N)]
+    for i, m in zip(range(A.LF_TILE - 3, A.LF_TILE + 3), (0b01, 0b10, 0b11, 0b01, 0b10, 0b00)):
+        if i < N:
+            items[i] = ("r", 4, m)
+    items[0], items[1] = ("r", 4, 0b11), ("w", 8)
+    if N > A.LF_TILE + 5:
+        items[A.LF_TILE + 4] = ("w", 9)
+        items[N - 1] = ("r", 4, 0b01)
+    return items
+
+
 @pytest.mark.parametrize("d", [-1, 0, 1])
 def test_tile_edges(ctx, d):
     """LF_TILE - 1, LF_TILE and LF_TILE + 1 rows (then two tiles more), with a
     group whose reads straddle the tile edge and a write on each side."""
     for extra in (0, 2 * A.LF_TILE):
-        N = A.LF_TILE + d + extra
-        items = [("x",) if i % 3 else ("i",) for i in range(N)]
-        for i, m in zip(range(A.LF_TILE - 3, A.LF_TILE + 3), (0b01, 0b10, 0b11, 0b01, 0b10, 0b00)):
-            if i < N:
-                items[i] = ("r", 4, m)
-        items[0], items[1] = ("r", 4, 0b11), ("w", 8)
-        if N > A.LF_TILE + 5:
-            items[A.LF_TILE + 4] = ("w", 9)
-            items[N - 1] = ("r", 4, 0b01)
+        items = tile_edge_items(A.LF_TILE + d + extra)
         want = agree(ctx, build(2, items), 2, maps=extra == 0)
         ms = [it[2] for it in items if it[0] == "r"]
         assert want["fork_groups"] == 1 and want["fork_count"] == ms.count(0b01) * ms.count(0b10) >= 1
+
+
+@pytest.mark.parametrize("shift", [0, 1])
+def test_device_columns(ctx, shift):
+    """The history of test_tile_edges' d = 1 in device memory, its columns
+    16-byte aligned (shift 0) and 8-byte aligned only (shift 1: the flag and
+    compact kernels load the rows of a pair one by one): every field and every
+    fork pair equal the host-column call's."""
+    from hipcols import DevCols
+    cols = build(2, tile_edge_items(A.LF_TILE + 1))
+    want = agree(ctx, cols, 2, maps=False)
+    assert want["fork_count"] >= 1
+    d = DevCols(cols, shift)
+    for path in (A.LF_PATH_AUTO,) + PATHS:
+        host = ctx.check_long_fork(cols, 2, path, fork_cap=want["fork_count"])
+        dev = ctx.check_long_fork(d, 2, path, fork_cap=want["fork_count"], on_device=True)
+        assert set(dev) == set(host)
+        for k, v in host.items():
+            if k == "forks":
+                assert dev[k].tolist() == v.tolist() == want["forks"].tolist(), path
+            elif k != "device_ms":
+                assert dev[k] == v, (k, path)
 
 
 def test_scattered_ranges(ctx):
