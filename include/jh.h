@@ -255,6 +255,12 @@ typedef struct jh_history {
  * of restarting it (JH_LIN_TAKEOVER); JH_LIN_NO_TAKEOVER forces it off. */
 #define JH_LIN_NO_TAKEOVER  16384
 #define JH_LIN_TAKEOVER     32768
+/* Round 8, not a test hook: the caller's jh_lin_opts and jh_summary have the
+ * fields added after ABI 8's layout (jh_lin_opts.bfs_stall_min,
+ * jh_summary.bfs_stall_picks). Additive to ABI 8: a caller built against the
+ * earlier layout never sets it, and the library then reads and writes nothing
+ * past that layout (the defaults apply). */
+#define JH_LIN_TAIL_FIELDS  65536
 
 typedef struct jh_lin_opts {
     int64_t init_value;        /* (model/cas-register init); JH_NIL = (cas-register) */
@@ -289,6 +295,11 @@ typedef struct jh_lin_opts {
                                   stall first; <=0: 4096. Not used when helper_late_us > 0 or
                                   JH_LIN_HELPERS_NOW / JH_LIN_HELP_STALL is set: those keep the
                                   time-based pick */
+    /* round 8, read only with JH_LIN_TAIL_FIELDS set in flags: */
+    int32_t bfs_stall_min;     /* the default race's reachable-set BFS takes the key whose sequential
+                                  search has the largest such stall, from this stall on, instead of
+                                  keys in list order (scheduling only); <=0: 4096 */
+    int32_t reserved;
 } jh_lin_opts;
 
 #define JH_DEFAULT_BUDGET (1 << 20)
@@ -375,6 +386,11 @@ typedef struct jh_summary {
     /* round 6: keys a late helper took over from the sequential search with
      * its saved state (the takeover; JH_LIN_NO_TAKEOVER: 0) */
     int64_t takeovers;
+    /* round 8, written only with JH_LIN_TAIL_FIELDS set in the call's flags:
+     * keys the reachable-set BFS took by their stall (0 on the paths that keep
+     * list order: JH_LIN_BFS_ONLY, JH_ALGO_LINEAR, JH_LIN_STREAM, a
+     * configurations request, no sequential LEAN wave) */
+    int64_t bfs_stall_picks;
 } jh_summary;
 
 typedef struct jh_ctx jh_ctx;

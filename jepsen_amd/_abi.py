@@ -70,6 +70,7 @@ LIN_SPEC_FIRST = 4096         # round 6: helpers serve posted spec jobs before t
 LIN_HELP_STALL = 8192         # round 6: helpers pick the keys stuck longest (no deeper layer)
 LIN_NO_TAKEOVER = 16384       # round 6: forces the takeover off
 LIN_TAKEOVER = 32768          # round 6 (opt-in): a helper continues the sequential search's saved state
+LIN_TAIL_FIELDS = 65536       # round 8: these structs carry bfs_stall_min / bfs_stall_picks (always set by _native)
 CAUSE_DEFERRED = 9
 
 
@@ -81,7 +82,8 @@ class JhLinOpts(C.Structure):
                 ("xw_waves", C.c_int32), ("p2_waves_per_cu", C.c_int32),
                 ("lean_waves", C.c_int32), ("wide_waves", C.c_int32),
                 ("handover_min", C.c_int32), ("p1_waves_per_cu", C.c_int32),
-                ("bfs_wgs", C.c_int32), ("helper_stall_min", C.c_int32)]       # ABI 7 (round 7: its reserved slot)
+                ("bfs_wgs", C.c_int32), ("helper_stall_min", C.c_int32),       # ABI 7 (round 7: its reserved slot)
+                ("bfs_stall_min", C.c_int32), ("reserved", C.c_int32)]         # round 8: read with LIN_TAIL_FIELDS
 
 
 # every field of jh_key_verdict: the parity tests compare all of them
@@ -117,7 +119,8 @@ class JhSummary(C.Structure):
                 ("resumed", C.c_int64), ("resume_bytes", C.c_int64),
                 # ABI 7: speculative dead-subtree enumerations (round 6)
                 ("spec_jobs", C.c_int64), ("spec_dead", C.c_int64), ("spec_merges", C.c_int64),
-                ("spec_nodes", C.c_int64), ("takeovers", C.c_int64)]
+                ("spec_nodes", C.c_int64), ("takeovers", C.c_int64),
+                ("bfs_stall_picks", C.c_int64)]                               # round 8: written with LIN_TAIL_FIELDS
 
 
 class JhLinConfig(C.Structure):

@@ -130,7 +130,7 @@ def _raise(rc, err):
 
 def _opts(init, budget, stream=0, algorithm=None, exact_count=True, **tune):
     """jh_lin_opts. tune: flags, quick_budget, phase2_budget, helpers,
-    helper_late_us, helper_stall_min, xw_waves, p2_waves_per_cu (jh.h; all decide the same
+    helper_late_us, helper_stall_min, bfs_stall_min, xw_waves, p2_waves_per_cu (jh.h; all decide the same
     verdicts, the tests use them to reach the less common search paths).
     exact_count: JH_LIN_EXACT_COUNT, WGL's cache size for every key (what the
     parity tests compare with the oracle); the checkers pass False -- their
@@ -149,6 +149,7 @@ def _opts(init, budget, stream=0, algorithm=None, exact_count=True, **tune):
         setattr(o, k, int(v))
     if exact_count:
         o.flags |= A.LIN_EXACT_COUNT
+    o.flags |= A.LIN_TAIL_FIELDS          # JhLinOpts / JhSummary have the round-8 fields
     return o
 
 

@@ -172,7 +172,7 @@ int jh_check_cas_independent(jh_ctx *ctx, const jh_history *h, const jh_lin_opts
         const int64_t K = h->n_keys;
         jh_key_verdict *dv = ctx->ws<jh_key_verdict>(WS_VERDICT, std::max<int64_t>(K, 1));
         if (K == 0) {
-            if (sum) { memset(sum, 0, sizeof *sum); sum->first_fail_entry = -1; }
+            if (sum) { memset(sum, 0, lin_summary_bytes(opts)); sum->first_fail_entry = -1; }
             return;
         }
         lin_check_independent(ctx, &d, opts, true, dv, sum, st);
@@ -193,7 +193,7 @@ int jh_check_cas_independent_device(jh_ctx *ctx, const jh_history *h, const jh_l
         HIP_TRY(hipSetDevice(ctx->device));
         hipStream_t st = opts && opts->stream ? (hipStream_t)(intptr_t)opts->stream : ctx->stream;
         if (h->n_keys == 0) {
-            if (sum) { memset(sum, 0, sizeof *sum); sum->first_fail_entry = -1; }
+            if (sum) { memset(sum, 0, lin_summary_bytes(opts)); sum->first_fail_entry = -1; }
             return;
         }
         lin_check_independent(ctx, h, opts, true, out_dev, sum, st);

@@ -135,6 +135,7 @@ enum WsSlot {
     WS_CY_FWD, WS_CY_BWD, WS_CY_CSR, WS_CY_STATE, WS_CY_LABEL, WS_CY_SIZE, WS_CY_KEYS, WS_CY_VALS,
     WS_CY_AP_META, WS_CY_AP_ROWS, WS_CY_AP_RECS, WS_CY_AP_LONGEST,
     WS_CY_MO_META, WS_CY_MO_ROWS, WS_CY_MO_RECS,
+    WS_BFS_TAKEN,
     WS_COUNT
 };
 
@@ -185,6 +186,14 @@ struct LinCfgReq {
     int32_t *n_dev;               // n_q, -1 on entry
     int64_t *rows_dev;            // n_q * per_key * 64
 };
+// Bytes of the caller's jh_lin_opts / jh_summary the library may touch: the
+// whole struct with JH_LIN_TAIL_FIELDS, else ABI 8's layout (jh.h)
+inline size_t lin_opts_bytes(const jh_lin_opts *o) {
+    return o && (o->flags & JH_LIN_TAIL_FIELDS) ? sizeof(jh_lin_opts) : offsetof(jh_lin_opts, bfs_stall_min);
+}
+inline size_t lin_summary_bytes(const jh_lin_opts *o) {
+    return o && (o->flags & JH_LIN_TAIL_FIELDS) ? sizeof(jh_summary) : offsetof(jh_summary, bfs_stall_picks);
+}
 void lin_check_independent(jh_ctx *ctx, const jh_history *dh, const jh_lin_opts *opts,
                            bool keyed, jh_key_verdict *out_dev, jh_summary *sum,
                            hipStream_t stream, const LinCfgReq *cfg = nullptr);

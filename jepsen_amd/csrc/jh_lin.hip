@@ -536,6 +536,9 @@ constexpr uint64_t HELPER_LATE_US = 250;
 // parent: 43.0), so 4 096 stays. At most HELPER_MAINS helpers run keys; the
 // others serve the spec board only.
 constexpr uint32_t HELPER_STALL_MIN = 4096;
+// Round 8: the BFS takes keys by the same stall, the largest first (bfs_pick),
+// from this stall on (jh_lin_opts.bfs_stall_min)
+constexpr uint32_t BFS_STALL_MIN = 4096;
 constexpr int HELPER_MAINS = 32;
 
 // write a key's verdict; in a race only the first finisher writes
@@ -4408,7 +4411,23 @@ struct BfsArgs {
     const int32_t *p1_done, *p1_tot;
     unsigned long long *t_span;
     unsigned long long *tl;     // -DJH_TUNING timeline: per key [0] BFS start, [1] end
+    // round 8, the default race (bfs_pick): keys by the stall their
+    // sequential search publishes instead of list order; null: list order.
+    // (One pointer to device memory, read between keys: every field here is
+    // live across bfs_key, whose registers are spilling already.)
+    const struct BfsPick *pk;
 };
+
+struct BfsPick {
+    const uint32_t *stall;      // per key: DfsArgs.stall of the sequential LEAN search
+    int32_t *taken;             // per key: a BFS workgroup has it (zeroed per call; not the helpers' flags)
+    const int32_t *seq_queue;   // the sequential LEAN search's queue, drained at seq_n
+    const int32_t *seq_exit;    // its waves that have left the queue (Q_SEQ_EXIT), of seq_waves
+    int32_t *picked;            // counter: keys taken by stall (jh_summary.bfs_stall_picks)
+    uint32_t stall_min;         // a key is a candidate at this stall or more
+    int32_t seq_n, seq_waves;
+};
+__global__ void k_bfs_pick_args(BfsPick *dst, BfsPick v) { *dst = v; }
 
 struct BfsShared {
     KeyInfo K;
@@ -4422,6 +4441,10 @@ struct BfsShared {
     uint32_t win_f[64];     // f, or 3 for no member
     unsigned long long cfg_min;
     unsigned gl_cnt[2], gl_ovf[2];   // the count pass's per-bucket LDS live sets (two in turn)
+    unsigned long long pick;         // bfs_pick: the best candidate, stall << 24 | inverted list index
+    unsigned long long t_enter;      // bfs_pick: the workgroup's start (thread 0's)
+    int open;                        // bfs_pick: the scan saw an unclaimed key
+    int list_done;                   // bfs_pick: this workgroup has seen the list-order queue exhausted (thread 0's)
 };
 
 static_assert(sizeof(BfsShared) <= BFS_HDR, "BFS header");
@@ -5709,6 +5732,100 @@ __device__ void bfs_key(const BfsArgs &A, BfsShared &sh, char *gscr, int tid, ui
     __syncthreads();
 }
 
+// Round 8, the default race (A.pk set): the workgroup's next key, by the
+// stall the key's sequential search publishes (DfsArgs.stall: inserts since
+// its deepest layer last rose) instead of list order. In list order the
+// workgroups sat on valid keys whose reachable sets are 11 to 400 times WGL's
+// cache until the sequential search claimed them, and the invalid keys -- the
+// keys this engine is needed for, whose stall only grows -- waited 7 to 15 ms
+// for a workgroup (profiles/r08/bfs_pick/). Sets sh.key (-1: leave), in order:
+//  1. the unclaimed, untaken key with the largest stall >= stall_min, ties to
+//     the lower list index (the late helpers take the smallest stall first, so
+//     the two engines meet on a key as late as possible), marked with a CAS
+//     on taken: the mark of this rule alone;
+//  2. none, and the sequential search has handed out its last key: the next
+//     unclaimed, untaken key in list order, handed out by the queue counter as
+//     before and not marked (the keys that never publish a stall: WIDE ones,
+//     searches short of their first 1 024-insert check). A key held this way
+//     that later crosses the minimum is still a candidate of rule 1, so a
+//     workgroup with nothing else to do may run it a second time: at most
+//     once more per key, the first verdict written wins (emit_verdict), and
+//     both runs count the same;
+//  3. none, and the sequential queue not drained: sleep ~50 us and scan again,
+//     instead of starting a list-order key to sit on;
+//  4. leave once the list-order pass is exhausted and every deferred key is
+//     claimed or every sequential wave has left its queue.
+constexpr unsigned long long BFS_WAIT_MAX_TICKS = 500000000ULL;   // 5 s of s_memrealtime, as HELPER_MAX_TICKS
+// (not inlined: inlined, k_lin_bfs's scratch grew from 868 to 884 bytes per
+// lane; as a call it stays at 868, with fewer spills than before the change)
+__device__ __attribute__((noinline)) void bfs_pick(const BfsArgs &A, BfsShared &sh, int tid) {
+    const BfsPick &P = *A.pk;
+    for (;;) {
+        if (tid == 0) { sh.pick = 0; sh.open = 0; }
+        __syncthreads();
+        for (int i = tid; i < A.n_list; i += BFS_THREADS) {
+            const int key = A.list[i];
+            if (__hip_atomic_load(&A.claim[key], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) continue;
+            sh.open = 1;
+            const uint32_t stl = __hip_atomic_load(&P.stall[key], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (stl < P.stall_min || __hip_atomic_load(&P.taken[key], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+                continue;
+            // (stall_min >= 1: a candidate's word is never 0, the empty pick)
+            atomicMax(&sh.pick, ((unsigned long long)stl << 24) | (unsigned long long)(0xFFFFFF - i));
+        }
+        __syncthreads();
+        if (tid == 0) {
+            int k = -2;                   // -2: sleep and scan again, -3: scan again at once
+            // past the watchdog the waits below are over: the list-order pass, then out
+            const bool late = __builtin_amdgcn_s_memrealtime() - sh.t_enter > BFS_WAIT_MAX_TICKS;
+            bool done = sh.list_done != 0;
+            if (sh.pick) {
+                const int key = A.list[0xFFFFFF - (int)(sh.pick & 0xFFFFFF)];
+                if (atomicCAS(&P.taken[key], 0, 1) == 0) { k = key; atomicAdd(P.picked, 1); }
+                else k = -3;              // another workgroup's: the next best
+            } else if (late || ld_agent(P.seq_queue) >= P.seq_n) {
+                while (!done) {
+                    const int idx = atomicAdd(A.queue, 1);
+                    if (idx >= A.n_list) { done = true; break; }
+                    const int key = A.list[idx];
+                    if (__hip_atomic_load(&A.claim[key], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ||
+                        __hip_atomic_load(&P.taken[key], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+                        continue;
+                    k = key;
+                    break;
+                }
+                sh.list_done = done;
+                // The exit cannot be missed. Every sequential wave leaves its
+                // queue whatever this kernel does: a search ends at its budget
+                // or when its key is claimed, a wave waits for nobody, and a
+                // block of that grid not yet resident waits only for blocks of
+                // its own grid to end. A wave raises Q_SEQ_EXIT after it has
+                // seen its queue empty, so seq_exit >= seq_waves (the LEAN
+                // blocks launched) implies the queue test above, and this
+                // branch runs on every scan that finds no candidate. A key
+                // is run at most once by its stall (the CAS) and once in list
+                // order (the queue counter), so the grid runs at most 2 x
+                // n_list keys, each bounded by reach_cap and its claim polls; between
+                // keys it scans, and a scan with no candidate ends here: with
+                // a list-order key, or with done set (after at most n_list +
+                // grid steps of the queue, which only grows). From then on
+                // the test below lets the workgroup go at the first scan
+                // after the last wave has left -- or sooner, when every key
+                // is claimed; or at the watchdog. A candidate found instead
+                // is a key run (bounded in number) or a lost CAS (the winner
+                // runs it), so scans with candidates do not go on forever.
+                if (k < 0 && done && (!sh.open || late || ld_agent(P.seq_exit) >= P.seq_waves)) k = -1;
+            }
+            sh.key = k;
+        }
+        __syncthreads();
+        const int k = sh.key;
+        if (k >= 0 || k == -1) return;
+        if (k == -2)
+            for (int j = 0; j < 16; j++) __builtin_amdgcn_s_sleep(127);   // ~50 us between scans
+    }
+}
+
 __global__ void __launch_bounds__(BFS_THREADS) k_lin_bfs(BfsArgs A0) {
     BfsShared &sh = *(BfsShared *)jh_lds;
     BfsArgs A = A0;                      // this workgroup's slices of the count buffers
@@ -5725,13 +5842,18 @@ __global__ void __launch_bounds__(BFS_THREADS) k_lin_bfs(BfsArgs A0) {
     uint64_t *front = A.front + (size_t)blockIdx.x * 2 * A.q_cap;
     char *gscr = A.scratch + (size_t)blockIdx.x * A.scratch_bytes;
     bool spanned = false;
+    if (A.pk && tid == 0) { sh.t_enter = __builtin_amdgcn_s_memrealtime(); sh.list_done = 0; }
     for (;;) {
-        if (tid == 0) {
-            const int idx = atomicAdd(A.queue, 1);
-            if (A.live_n) sh.key = stream_key(A.list, A.live_n, A.p1_done, A.p1_tot, idx, A.src.flags);
-            else sh.key = idx < A.n_list ? A.list[idx] : -1;
+        if (A.pk) {
+            bfs_pick(A, sh, tid);
+        } else {
+            if (tid == 0) {
+                const int idx = atomicAdd(A.queue, 1);
+                if (A.live_n) sh.key = stream_key(A.list, A.live_n, A.p1_done, A.p1_tot, idx, A.src.flags);
+                else sh.key = idx < A.n_list ? A.list[idx] : -1;
+            }
+            __syncthreads();
         }
-        __syncthreads();
         const int key = sh.key;
         if (key < 0) break;
         if (A.t_span && !spanned && tid == 0) atomicMin(&A.t_span[0], __builtin_amdgcn_s_memrealtime());
@@ -6826,6 +6948,7 @@ struct LinRun {
     uint64_t *race_lean_sizing(int nd_l, int help_cus);
     void race_helpers(int nd_l);
     void race_lean_args(int nd_l, uint64_t *memo2);
+    void race_bfs_pick(int nd_l);
     void timeline_tables(bool wide);
     DfsArgs phase1_wide_args() const;
     DfsArgs phase3_lean_args() const;
@@ -7368,6 +7491,14 @@ void LinRun::race_bfs(int nd_all) {
     // for more (C4's shard, 4 258 deferred keys, 812 of them invalid ones
     // the BFS settles: 209.7 -> 202.0 ms); profiles/r06/ab_bfs_helpers/,
     // ab_c4_split/. A measured band, not a model of the race.
+    // Round 8, with the pick by stall (bfs_pick) the workgroups sleep most
+    // of the phase (C3 rank 0: 510 workgroup-ms of key runs in 64 x 26), yet
+    // fewer do not pay: the CUs they free get sequential waves whose queue
+    // is drained at 7.6 ms anyway, and the invalid keys -- 72, all
+    // candidates within ~3 ms of each other -- queue for workgroups. C3 rank
+    // 0, ms per step, three alternating runs (profiles/r08/bfs_pick/):
+    //   64: 35.53 35.53 35.63   48: 35.98 36.34 35.97   32: 36.65 36.76 37.04
+    // So 64 stays.
     const int bfs_cus = std::max(1, nd_all > 2000 && nd_all <= 4000 ? ctx->n_cu / 4
                                                                       : std::min(96, ctx->n_cu * 3 / 8));
     wg2 = std::min(nd_all, tune_env("JH_BFS_CUS") ? std::max(1, atoi(tune_env("JH_BFS_CUS"))) :
@@ -7379,7 +7510,9 @@ void LinRun::race_bfs(int nd_all) {
     uint64_t *bset = ctx->ws<uint64_t>(WS_BFS_SET, (size_t)wg2 * set_cap);
     uint64_t *bq = ctx->ws<uint64_t>(WS_BFS_Q, (size_t)wg2 * 4 * q_cap);
     char *bscr = ctx->ws<char>(WS_SCRATCH_BFS, (size_t)wg2 * scr_bytes_bfs);
-    int32_t *unres = ctx->ws<int32_t>(WS_BFS_META, nd_all + 1);
+    // (twice the keys: with the pick by stall a key can be run once in list
+    // order and once by its stall, bfs_pick, and be given up both times)
+    int32_t *unres = ctx->ws<int32_t>(WS_BFS_META, 2 * (size_t)nd_all + 1);
     c = BfsArgs{};
     c.src = key_src();
     c.list = defer; c.n_list = nd_all; c.queue = q + Q_QUEUE; c.out = out_dev;
@@ -7571,6 +7704,35 @@ void LinRun::race_lean_args(int nd_l, uint64_t *memo2) {
         b.hlog = ctx->ws<uint32_t>(WS_RS_LOG2, (size_t)wmax * b.hlog_cap);
         wh.d.handoff = ho;
     }
+}
+
+// Round 8, the default race with sequential LEAN waves (run_race; not the
+// streaming pass, the workgroup race or JH_LIN_BFS_ONLY): the BFS takes keys
+// by the stall those waves publish (bfs_pick). The stalls are published with
+// or without helpers, and the waves count their exits for the BFS's own exit.
+// writes: seq_stall (without helpers), the stall and exit fields of b, c.pk
+void LinRun::race_bfs_pick(int nd_l) {
+    if (bfs_only || wg_race || waves2 <= 0 || nd_l <= 0) return;
+    // the pick's arguments (32 words), then [0, K): the BFS's taken flags;
+    // [K, 2K): the stalls when no helper allocated them
+    int32_t *buf = ctx->ws<int32_t>(WS_BFS_TAKEN, 32 + 2 * (size_t)K);
+    static_assert(sizeof(BfsPick) <= 32 * sizeof(int32_t), "BfsPick");
+    int32_t *taken = buf + 32;
+    HIP_TRY(hipMemsetAsync(taken, 0, (seq_stall ? 1 : 2) * (size_t)K * sizeof(int32_t), st));
+    if (!seq_stall) seq_stall = (uint32_t *)(taken + K);
+    b.stall = seq_stall;
+    b.exit_count = q + Q_SEQ_EXIT;
+    BfsPick pk{};
+    pk.stall = seq_stall;
+    pk.stall_min = opts && (opts->flags & JH_LIN_TAIL_FIELDS) && opts->bfs_stall_min > 0 ? (uint32_t)opts->bfs_stall_min
+                                                                                       : BFS_STALL_MIN;
+    pk.taken = taken;
+    pk.seq_queue = q + Q_P2_QUEUE; pk.seq_n = nd_l;
+    pk.seq_exit = q + Q_SEQ_EXIT; pk.seq_waves = waves2;
+    pk.picked = q + Q_BFS_PICKS;
+    k_bfs_pick_args<<<1, 1, 0, st>>>((BfsPick *)buf, pk);
+    HIP_TRY(hipGetLastError());
+    c.pk = (const BfsPick *)buf;
 }
 
 // tuning builds (JH_DEFER_TIMES): per key [BFS start, end, sequential start,
@@ -8018,6 +8180,7 @@ void LinRun::run_linear() {
 // writes: prep_race's and prep_wide's; b.rs_mode, the handoff fields
 void LinRun::run_race() {
     prep_race(n_defer, n_def_l);
+    race_bfs_pick(n_def_l);
     if (resume) b.rs_mode = 2;      // (and phase 3, c3 = b: a record is replaced only by a takeover's newer one)
     if (!resume) { b.handoff = nullptr; wh.d.handoff = nullptr; }   // (a takeover continues from records)
     timeline_tables(/*wide=*/true);
@@ -8128,6 +8291,7 @@ void LinRun::fill_summary(const long long *sh) {
     sum->p2_start_ms = -1; sum->p1_span_ms = 0;
     sum->resumed = resume ? qh[Q_RS_PUBLISHED] : 0;
     sum->takeovers = resume ? qh[Q_RS_TAKEOVERS] : 0;
+    if (opts && (opts->flags & JH_LIN_TAIL_FIELDS)) sum->bfs_stall_picks = qh[Q_BFS_PICKS];
     sum->spec_nodes = q64(qh, Q_SPEC); sum->spec_merges = qh[Q_SPEC_MERGES];
     sum->spec_jobs = qh[Q_SPEC_JOBS]; sum->spec_dead = qh[Q_SPEC_DEAD];
     sum->resume_bytes = resume ? q64(qh, Q_RS_USED) : 0;

@@ -270,7 +270,8 @@ int multi_check_cas_independent(jh_ctx *g, const jh_history *h, const jh_lin_opt
         snprintf(err, errlen, "multi-device split: %s", e.what());
         return JH_ENOMEM;
     }
-    jh_lin_opts o = opts ? *opts : jh_lin_opts{JH_NIL, 0, 0};
+    jh_lin_opts o{JH_NIL, 0, 0};
+    if (opts) memcpy(&o, opts, lin_opts_bytes(opts));   // (a caller's struct may end at ABI 8's layout)
     o.stream = 0;                                   // each device runs on its own ctx stream
     const bool two_stage = o.algorithm != JH_ALGO_LINEAR && !(o.flags & (JH_LIN_PHASE1_ONLY | JH_LIN_SKIP_PHASE1));
     jh_lin_opts o1 = o;
@@ -375,6 +376,7 @@ int multi_check_cas_independent(jh_ctx *g, const jh_history *h, const jh_lin_opt
                     s[d].wide_probes += ss.wide_probes; s[d].helper_probes += ss.helper_probes;
                     s[d].seq_ms += ss.seq_ms; s[d].bfs_ms += ss.bfs_ms; s[d].wide_ms += ss.wide_ms;
                     s[d].p3_ms += ss.p3_ms; s[d].n_phase3 += ss.n_phase3; s[d].n_phase3_wide += ss.n_phase3_wide;
+                    if (o2.flags & JH_LIN_TAIL_FIELDS) s[d].bfs_stall_picks += ss.bfs_stall_picks;
                 }
             });
         for (auto &x : th) x.join();
@@ -414,11 +416,12 @@ int multi_check_cas_independent(jh_ctx *g, const jh_history *h, const jh_lin_opt
         m.xw_ms = std::max(m.xw_ms, a.xw_ms);
         m.p3_probes += a.p3_probes; m.wide_probes += a.wide_probes; m.xw_probes += a.xw_probes;
         m.helper_probes += a.helper_probes; m.n_deferred_wide += a.n_deferred_wide;
+        if (o.flags & JH_LIN_TAIL_FIELDS) m.bfs_stall_picks += a.bfs_stall_picks;
         m.n_phase3 += a.n_phase3; m.n_phase3_wide += a.n_phase3_wide; m.n_xw += a.n_xw;
         m.lean_entries += a.lean_entries; m.wide_entries += a.wide_entries; m.xw_entries += a.xw_entries;
         for (int i = 0; i < 4; i++) m.waves[i] = std::max(m.waves[i], a.waves[i]);
     }
-    if (sum) *sum = m;
+    if (sum) memcpy(sum, &m, lin_summary_bytes(&o));
     if (err && errlen) err[0] = 0;
     return JH_OK;
 }

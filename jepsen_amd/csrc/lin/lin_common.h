@@ -38,6 +38,7 @@ namespace {
 //   84-85   Q_ENT_P3
 //   88-89   Q_RS_USED, 90 Q_RS_PUBLISHED, 91 Q_RS_TAKEOVERS
 //   92      Q_MAINS
+//   93      Q_BFS_PICKS   keys the BFS took by their stall (round 8)
 //   96-97   Q_SPEC, 98 Q_SPEC_MERGES, 99 Q_SPEC_JOBS, 100 Q_SPEC_DEAD
 constexpr int Q_WORDS = 104;
 constexpr int Q_QUEUE = 0, Q_DEFER = 1, Q_FLAGS = 2, Q_UNRES = 3, Q_PROBES_P1 = 4;
@@ -59,6 +60,7 @@ constexpr int Q_ENT_P3 = 84;        // entries of the LEAN keys restarted in pha
 constexpr int Q_RS_USED = 88;       // [88..89] resume records' bytes, [90] records published (round 5), [91] takeovers (round 6)
 constexpr int Q_RS_PUBLISHED = 90, Q_RS_TAKEOVERS = 91;
 constexpr int Q_MAINS = 92;         // round 6: late helpers running a key now
+constexpr int Q_BFS_PICKS = 93;     // round 8: keys k_lin_bfs took by their published stall (bfs_pick)
 constexpr int Q_SPEC = 96;          // round 6: [96..97] merged nodes, [98] merges, [99] spec jobs, [100] dead results
 constexpr int Q_SPEC_MERGES = 98, Q_SPEC_JOBS = 99, Q_SPEC_DEAD = 100;
 // bits of the flags word q[Q_FLAGS]: any of them fails the call (JH_EDEVICE)
