@@ -27,6 +27,10 @@
  *                                                   jepsen/src/jepsen/tests/long_fork.clj:158-324
  *   jh_check_causal_reverse   <- (independent/checker (jepsen.tests.causal-reverse/checker))
  *                                                   jepsen/src/jepsen/tests/causal_reverse.clj:21-84
+ *   jh_check_causal           <- (independent/checker (jepsen.tests.causal/check (causal-register)))
+ *                                                   jepsen/src/jepsen/tests/causal.clj:33-110
+ *   jh_check_g2               <- (jepsen.tests.adya/g2-checker)
+ *                                                   jepsen/src/jepsen/tests/adya.clj:62-88
  *   jh_check_cycle            <- (jepsen.tests.cycle/checker (cycle/combine ...))
  *                                                   jepsen/src/jepsen/tests/cycle.clj:202-216,911-934
  *   jh_scc                    <- cycle/tarjan       jepsen/src/jepsen/tests/cycle.clj:150-160
@@ -101,6 +105,16 @@
  * and [] are b = 0, and then a is not looked at). f = JH_F_APPEND: a = the
  * element, b = 0. Elements are int64 and never JH_NIL; k is dense,
  * 0 <= k < n_keys.
+ *
+ * Causal ops (jh_check_causal only): f = JH_F_READ / JH_F_WRITE /
+ * JH_F_READ_INIT or an interned id >= 16, value = :value (JH_NIL for nil),
+ * value2 unused (0); aux holds 2 n words, aux[2 i] = row i's :position and
+ * aux[2 i + 1] = its :link, nil as JH_NIL and :init as JH_CAUSAL_INIT. Values,
+ * positions and links are longs in (INT64_MIN + 1, INT64_MAX]; only :ok rows are
+ * read. `key` as in jh_check_cas_independent.
+ *
+ * G2 ops (jh_check_g2 only): f = JH_F_INSERT for :insert, anything else
+ * otherwise; key = the interned (key (:value op)). Only type, f and key are read.
  */
 #ifndef JH_H
 #define JH_H
@@ -1064,6 +1078,102 @@ int jh_scc(jh_ctx *ctx, int64_t n_vertices, const int64_t *src, const int64_t *d
 int jh_check_cycle(jh_ctx *ctx, const jh_history *h, const jh_cycle_opts *opts, jh_cycle_result *res,
                    int64_t *labels_out, int64_t *scc_off, int64_t *scc_rows, int64_t scc_cap, int64_t rows_cap,
                    int64_t *edges_out, int64_t edge_cap, char *err, size_t errlen);
+
+/* (independent/checker (jepsen.tests.causal/check (causal-register))),
+ * tests/causal.clj:33-110 (additive to ABI 8: new structs, two f codes, one
+ * sentinel and one symbol), batched over the keys of an independent history.
+ *
+ * Causal ops (jh_check_causal only): the standard columns, key = the interned
+ * independent key. f = JH_F_READ, JH_F_WRITE, JH_F_READ_INIT or an interned id
+ * >= 16; value = :value (JH_NIL = nil); value2 is not read (0). aux holds 2 n
+ * words: aux[2 i] = row i's :position and aux[2 i + 1] = its :link, JH_NIL for
+ * nil / absent, JH_CAUSAL_INIT for the keyword :init. Values, positions and
+ * links are longs in (INT64_MIN + 1, INT64_MAX]; anything else has no encoding
+ * (the shim then checks on the host). Only :ok rows are read.
+ *
+ * Per key, over its :ok rows in history order, the register (value, counter,
+ * last-pos) starts at (0, 0, nil). In a valid prefix value = counter = the
+ * number of :ok writes so far and last-pos = the :position of the key's
+ * previous :ok row, so every row is judged on its own from w = the key's :ok
+ * writes before it and p = the position of the key's previous :ok row (JH_NIL
+ * for the first). A row is an EVENT of
+ *   kind 1  link != JH_CAUSAL_INIT and link != p (nil = nil passes);
+ *   kind 2  a write of value != w + 1 (nil included);
+ *   kind 3  a read-init with w = 0 and value != 0 (nil included), or with a
+ *           value that is neither nil nor w;
+ *   kind 4  a read of a value that is neither nil nor w;
+ *   kind 5  any other f (the reference's condp throws; the link check comes
+ *           first, so a bad link makes it kind 1).
+ * The key's first event decides: kinds 1-4 JH_INVALID, kind 5 JH_UNKNOWN, no
+ * event JH_VALID with the final model (counter, counter, last_pos).
+ *
+ * keys_out (may be NULL) receives max(n_keys, 1) jh_causal_key. An un-keyed
+ * history (key == NULL or n_keys == 0) is one key 0. A key without :ok rows is
+ * valid with counter 0 and last_pos JH_NIL.
+ *
+ * JH_EINVAL: n_aux != 2 n, an :ok row's key >= n_keys. JH_EUNSUPPORTED (the
+ * shim falls back): in a keyed history an :ok row of a process >= 0 without a
+ * key (it would belong to every key; such a row of a process < 0 is skipped,
+ * the shim does not send one); more than 2^31 - 2 :ok rows, 2^32 - 1 rows or
+ * 2^30 keys. */
+#define JH_F_INSERT    8                 /* adya g2: :insert */
+#define JH_F_READ_INIT 9                 /* causal: :read-init */
+#define JH_CAUSAL_INIT (INT64_MIN + 1)   /* a :link of :init */
+
+typedef struct jh_causal_opts {
+    int64_t reserved[4];
+} jh_causal_opts;
+
+typedef struct jh_causal_key {   /* one per key */
+    int32_t valid;               /* JH_VALID / JH_INVALID / JH_UNKNOWN */
+    int32_t kind;                /* 0 none, 1 link, 2 write, 3 read-init, 4 read, 5 unknown f */
+    int64_t row;                 /* the event row; -1 when valid */
+    int64_t counter;             /* :ok writes of the key before `row`; all of them when valid */
+    int64_t last_pos;            /* position of the key's previous :ok row (valid: of its last); JH_NIL: nil / none */
+} jh_causal_key;
+
+typedef struct jh_causal_result {
+    int32_t valid, cause;          /* invalid outranks unknown outranks valid; JH_CAUSE_BAD_F when some key is unknown */
+    int64_t ok_count;              /* :ok rows judged */
+    int64_t invalid_keys, unknown_keys;
+    int64_t first_event_row;       /* the smallest event row of any key; -1 when there is none */
+    double device_ms;
+} jh_causal_result;
+
+int jh_check_causal(jh_ctx *ctx, const jh_history *h, const jh_causal_opts *opts, jh_causal_result *res,
+                    jh_causal_key *keys_out, char *err, size_t errlen);
+
+/* (jepsen.tests.adya/g2-checker), tests/adya.clj:62-88 (additive to ABI 8: new
+ * structs and one symbol): at most one :insert completes :ok for any key.
+ *
+ * G2 ops (jh_check_g2 only): the standard columns. f = JH_F_INSERT for :insert,
+ * anything else otherwise; key = the interned (key (:value op)). Only type, f
+ * and key are read. Every insert row, of any type and any process, makes its
+ * key present; an :ok insert adds one to the key's count.
+ *   key_count      keys present
+ *   illegal_count  keys with a count > 1
+ *   legal_count    keys with a count > 0, less illegal_count
+ * illegal_out (may be NULL) receives the first min(illegal_count, illegal_cap)
+ * pairs [key id, count] in ascending key id. first_illegal_row = the smallest
+ * row that is an :ok insert of an illegal key and not that key's first :ok
+ * insert, or -1. Every result field is exact whatever the cap is.
+ *
+ * JH_EINVAL: an insert row's key >= n_keys. JH_EUNSUPPORTED: an insert row
+ * without a key (the reference throws); more than 2^31 - 2 rows. */
+typedef struct jh_g2_opts {
+    int64_t reserved[4];
+} jh_g2_opts;
+
+typedef struct jh_g2_result {
+    int32_t valid, cause;          /* JH_VALID / JH_INVALID; cause is JH_CAUSE_NONE */
+    int64_t key_count, legal_count, illegal_count;
+    int64_t insert_rows;
+    int64_t first_illegal_row;     /* -1 when there is none */
+    double device_ms;
+} jh_g2_result;
+
+int jh_check_g2(jh_ctx *ctx, const jh_history *h, const jh_g2_opts *opts, jh_g2_result *res,
+                int64_t *illegal_out, int64_t illegal_cap, char *err, size_t errlen);
 
 #ifdef __cplusplus
 }

@@ -275,6 +275,40 @@ CAUSE_DUPLICATE_APPENDS, CAUSE_DUPLICATE_ELEMENTS, CAUSE_NO_TOTAL_ORDER, CAUSE_N
 CAUSES.update({13: "duplicate-appends", 14: "duplicate-elements", 15: "no-total-state-order", 16: "no-writer"})
 
 
+# jepsen.tests.causal and adya/g2-checker (additive to ABI 8)
+F_INSERT, F_READ_INIT = 8, 9  # JH_F_INSERT, JH_F_READ_INIT
+CAUSAL_INIT = NIL + 1         # JH_CAUSAL_INIT: a :link of :init
+CAUSE_BAD_F = 5
+CM_TILE = 1024                # sorted slots per tile of jh_causalreg.hip's judge kernel (the tests straddle its edges)
+CM_FLAG_TILE = 2048           # rows per tile of its flag pass
+G2_TILE = 2048                # keys per tile of jh_g2.hip's key pass
+CM_KINDS = {0: None, 1: "link", 2: "write", 3: "read-init", 4: "read", 5: "unknown-f"}
+
+
+class JhCausalOpts(C.Structure):
+    _fields_ = [("reserved", C.c_int64 * 4)]
+
+
+class JhCausalKey(C.Structure):
+    _fields_ = [("valid", C.c_int32), ("kind", C.c_int32), ("row", C.c_int64), ("counter", C.c_int64),
+                ("last_pos", C.c_int64)]
+
+
+class JhCausalResult(C.Structure):
+    _fields_ = [("valid", C.c_int32), ("cause", C.c_int32), ("ok_count", C.c_int64), ("invalid_keys", C.c_int64),
+                ("unknown_keys", C.c_int64), ("first_event_row", C.c_int64), ("device_ms", C.c_double)]
+
+
+class JhG2Opts(C.Structure):
+    _fields_ = [("reserved", C.c_int64 * 4)]
+
+
+class JhG2Result(C.Structure):
+    _fields_ = [("valid", C.c_int32), ("cause", C.c_int32), ("key_count", C.c_int64), ("legal_count", C.c_int64),
+                ("illegal_count", C.c_int64), ("insert_rows", C.c_int64), ("first_illegal_row", C.c_int64),
+                ("device_ms", C.c_double)]
+
+
 class JhCycleOpts(C.Structure):
     _fields_ = [("analyzers", C.c_int32), ("path", C.c_int32), ("extra_src", _p64), ("extra_dst", _p64),
                 ("n_extra", C.c_int64), ("reserved", C.c_int64 * 4)]
@@ -296,8 +330,12 @@ try:
                                ("fail_entry", _np.int64), ("explored", _np.int64),
                                ("previous_ok", _np.int64), ("last_op", _np.int64),
                                ("analyzer", _np.int32), ("reserved", _np.int32)])
+    # ... and as jh_causal_key
+    CAUSAL_KEY_DTYPE = _np.dtype([("valid", _np.int32), ("kind", _np.int32), ("row", _np.int64),
+                                  ("counter", _np.int64), ("last_pos", _np.int64)])
 except Exception:  # pragma: no cover
     VERDICT_DTYPE = None
+    CAUSAL_KEY_DTYPE = None
 
 
 def ptr64(a):

@@ -78,6 +78,10 @@ def lib():
             L.jh_check_causal_reverse.argtypes = [C.c_void_p, H, C.POINTER(A.JhCausalReverseOpts),
                                                   C.POINTER(A.JhCausalReverseResult), C.POINTER(C.c_int32), p64,
                                                   C.c_int64, p64, C.c_int64, C.c_char_p, C.c_size_t]
+            L.jh_check_causal.argtypes = [C.c_void_p, H, C.POINTER(A.JhCausalOpts), C.POINTER(A.JhCausalResult),
+                                          C.POINTER(A.JhCausalKey), C.c_char_p, C.c_size_t]
+            L.jh_check_g2.argtypes = [C.c_void_p, H, C.POINTER(A.JhG2Opts), C.POINTER(A.JhG2Result), p64, C.c_int64,
+                                      C.c_char_p, C.c_size_t]
             L.jh_scc.argtypes = [C.c_void_p, C.c_int64, p64, p64, C.c_int64, C.POINTER(A.JhCycleOpts),
                                  C.POINTER(A.JhCycleResult), p64, p64, p64, C.c_int64, C.c_int64, C.c_char_p, C.c_size_t]
             L.jh_check_cycle.argtypes = [C.c_void_p, H, C.POINTER(A.JhCycleOpts), C.POINTER(A.JhCycleResult), p64, p64,
@@ -116,6 +120,7 @@ EXPORTED_SYMBOLS = ["jh_version", "jh_open", "jh_open_multi", "jh_open_devices",
                     "jh_check_cas", "jh_check_cas_independent_device", "jh_lin_configs", "jh_check_counter",
                     "jh_check_set", "jh_check_set_bitmaps", "jh_check_set_full", "jh_check_set_full_opts", "jh_check_total_queue", "jh_check_queue",
                     "jh_check_unique_ids", "jh_check_bank", "jh_check_long_fork", "jh_check_causal_reverse",
+                    "jh_check_causal", "jh_check_g2",
                     "jh_scc", "jh_check_cycle",
                     "jh_host_alloc", "jh_host_free",
                     # include/jh_io.h
@@ -532,6 +537,38 @@ class Context:
         out["errors"] = (errs[:5 * min(r.error_count, ecap)] if ecap else np.zeros(0, np.int64)).reshape(-1, 5)
         out["missing"] = miss[:min(r.missing_total, mcap)] if mcap else np.zeros(0, np.int64)
         return out
+
+    # -- causal ---------------------------------------------------------------
+    def check_causal(self, cols, on_device=False, keys=True):
+        """jh_check_causal: the result fields plus `keys`, a structured array
+        (A.CAUSAL_KEY_DTYPE) of max(n_keys, 1) records; None when not asked
+        for (a NULL keys_out)."""
+        h = A.make_history(cols, on_device=on_device)
+        out = np.zeros(max(int(cols.n_keys), 1), A.CAUSAL_KEY_DTYPE) if keys else None
+        r, o = A.JhCausalResult(), A.JhCausalOpts()
+        err = C.create_string_buffer(1024)
+        rc = lib().jh_check_causal(self._h, C.byref(h), C.byref(o), C.byref(r),
+                                   out.ctypes.data_as(C.POINTER(A.JhCausalKey)) if keys else None, err, len(err))
+        _raise(rc, err)
+        res = {name: getattr(r, name) for name, _ in A.JhCausalResult._fields_}
+        res["keys"] = out
+        return res
+
+    # -- adya g2 --------------------------------------------------------------
+    def check_g2(self, cols, illegal_cap=0, on_device=False):
+        """jh_check_g2: the result fields plus `illegal`, a (k, 2) array of
+        [key id, count], k = min(illegal_count, illegal_cap), in ascending key
+        id. A cap of 0 passes a NULL pointer."""
+        h = A.make_history(cols, on_device=on_device)
+        cap = max(int(illegal_cap), 0)
+        pairs = np.zeros(2 * cap, np.int64) if cap else None
+        r, o = A.JhG2Result(), A.JhG2Opts()
+        err = C.create_string_buffer(1024)
+        rc = lib().jh_check_g2(self._h, C.byref(h), C.byref(o), C.byref(r), A.ptr64(pairs), cap, err, len(err))
+        _raise(rc, err)
+        res = {name: getattr(r, name) for name, _ in A.JhG2Result._fields_}
+        res["illegal"] = (pairs[:2 * min(r.illegal_count, cap)] if cap else np.zeros(0, np.int64)).reshape(-1, 2)
+        return res
 
     # -- cycle ----------------------------------------------------------------
     @staticmethod

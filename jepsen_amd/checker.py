@@ -686,5 +686,9 @@ from . import bank  # noqa: E402,F401
 from . import long_fork  # noqa: E402,F401
 # and jepsen.tests.causal-reverse (tests/causal_reverse.clj): checker.causal_reverse.checker()
 from . import causal_reverse  # noqa: E402,F401
+# and jepsen.tests.causal (tests/causal.clj): checker.causal.check(checker.causal.causal_register()),
+# and jepsen.tests.adya (tests/adya.clj): checker.adya.g2_checker()
+from . import causal  # noqa: E402,F401
+from . import adya  # noqa: E402,F401
 # and jepsen.tests.cycle (tests/cycle.clj): checker.cycle.checker(analyze_fn)
 from . import cycle  # noqa: E402,F401

@@ -563,6 +563,38 @@ int jh_check_causal_reverse(jh_ctx *ctx, const jh_history *h, const jh_causal_re
     });
 }
 
+int jh_check_causal(jh_ctx *ctx, const jh_history *h, const jh_causal_opts *opts, jh_causal_result *res,
+                    jh_causal_key *keys_out, char *err, size_t errlen) {
+    if (!ctx || !res || !opts) { set_err(err, errlen, "null argument"); return JH_EINVAL; }
+    ctx = primary(ctx);
+    std::lock_guard<std::mutex> g(ctx->mu);
+    return guarded(err, errlen, [&] {
+        check_hist(h);
+        if (h->n_aux != 2 * h->n) throw_jh(JH_EINVAL, "causal: n_aux must be 2 n (a position and a link per row)");
+        if (h->n > 0 && !h->aux) throw_jh(JH_EINVAL, "causal: n_aux > 0 without aux");
+        HIP_TRY(hipSetDevice(ctx->device));
+        const bool keyed = h->key != nullptr && h->n_keys > 0;
+        jh_history d = stage_history(ctx, h, keyed, true);
+        if (!keyed) d.key = nullptr;
+        causal_check(ctx, &d, res, keys_out, ctx->stream);
+    });
+}
+
+int jh_check_g2(jh_ctx *ctx, const jh_history *h, const jh_g2_opts *opts, jh_g2_result *res, int64_t *illegal_out,
+                int64_t illegal_cap, char *err, size_t errlen) {
+    if (!ctx || !res || !opts) { set_err(err, errlen, "null argument"); return JH_EINVAL; }
+    ctx = primary(ctx);
+    std::lock_guard<std::mutex> g(ctx->mu);
+    return guarded(err, errlen, [&] {
+        check_hist(h);
+        HIP_TRY(hipSetDevice(ctx->device));
+        const bool keyed = h->key != nullptr && h->n_keys > 0;
+        jh_history d = stage_history(ctx, h, keyed, false);
+        if (!keyed) d.key = nullptr;
+        g2_check(ctx, &d, res, illegal_out, illegal_cap, ctx->stream);
+    });
+}
+
 int jh_scc(jh_ctx *ctx, int64_t n_vertices, const int64_t *src, const int64_t *dst, int64_t n_edges,
            const jh_cycle_opts *opts, jh_cycle_result *res, int64_t *labels_out, int64_t *scc_off, int64_t *scc_rows,
            int64_t scc_cap, int64_t rows_cap, char *err, size_t errlen) {

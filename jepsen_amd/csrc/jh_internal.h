@@ -136,6 +136,8 @@ enum WsSlot {
     WS_CY_AP_META, WS_CY_AP_ROWS, WS_CY_AP_RECS, WS_CY_AP_LONGEST,
     WS_CY_MO_META, WS_CY_MO_ROWS, WS_CY_MO_RECS,
     WS_BFS_TAKEN,
+    WS_CM_META, WS_CM_WORDS, WS_CM_TCNT, WS_CM_TBASE, WS_CM_TMP, WS_CM_KEY, WS_CM_ROW, WS_CM_OFF, WS_CM_SUM, WS_CM_EV, WS_CM_OUT,
+    WS_G2_META, WS_G2_CNT, WS_G2_WORDS, WS_G2_TCNT, WS_G2_TBASE, WS_G2_TMP, WS_G2_MIN, WS_G2_OUT,
     WS_COUNT
 };
 
@@ -229,6 +231,11 @@ void long_fork_check(jh_ctx *ctx, const jh_history *dh, const jh_long_fork_opts 
 void causal_reverse_check(jh_ctx *ctx, const jh_history *dh, const jh_causal_reverse_opts *opts,
                           jh_causal_reverse_result *res, int32_t *key_valid, int64_t *errors_out, int64_t err_cap,
                           int64_t *missing_out, int64_t missing_cap, hipStream_t stream);
+// causal (jh_causalreg.hip); keys_out = max(n_keys, 1) host records
+void causal_check(jh_ctx *ctx, const jh_history *dh, jh_causal_result *res, jh_causal_key *keys_out, hipStream_t stream);
+// adya g2 (jh_g2.hip); illegal_out = [key id, count] pairs
+void g2_check(jh_ctx *ctx, const jh_history *dh, jh_g2_result *res, int64_t *illegal_out, int64_t illegal_cap,
+              hipStream_t stream);
 // cycle (jh_cycle.hip); src / dst are host edge lists, the outputs host buffers (any may be null)
 struct CycleOut {
     int64_t *labels, *scc_off, *scc_rows, scc_cap, rows_cap, *edges, edge_cap;

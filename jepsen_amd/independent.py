@@ -5,13 +5,15 @@ is (or composes) a cas-register `linearizable`, the whole history is encoded
 once and ALL keys are checked by one libjh call (splitter + per-key WGL on
 the GPU); any other composed checkers still run per key on their own. When it
 is (or composes) a causal-reverse checker, every key's reads are judged by one
-jh_check_causal_reverse call in the same way.
+jh_check_causal_reverse call in the same way, and a causal checker over
+(causal-register) judges every key with one jh_check_causal call.
 """
 from . import _abi as A
 from . import history as H
 from .checker import (Checker, Compose, Linearizable, _algorithm, add_configs, check_safe, lin_result, merge_valid,
                       wants_configs, _init_state, _ctx)
 from .causal_reverse import CausalReverseChecker, check_independent as _cr_check_independent
+from .causal import CausalChecker, check_independent as _cm_check_independent
 from .model import to_device_ops
 
 DIR = "independent"
@@ -110,6 +112,16 @@ def _cr_member(inner):
     return None, None
 
 
+def _cm_member(inner):
+    if isinstance(inner, CausalChecker) and inner.on_device():
+        return None, inner
+    if isinstance(inner, Compose):
+        for name, c in inner.checker_map.items():
+            if isinstance(c, CausalChecker) and c.on_device():
+                return name, c
+    return None, None
+
+
 class IndependentChecker(Checker):
     """independent.clj:247-298."""
 
@@ -183,6 +195,25 @@ class IndependentChecker(Checker):
                 r = {}
                 for nm, c in self.inner.checker_map.items():
                     r[nm] = res if nm == cr_name else check_safe(
+                        c, test, subs[key], {"subdirectory": [DIR, key], "history-key": key})
+                r["valid?"] = merge_valid(x.get("valid?") if isinstance(x, dict) else None for x in r.values())
+                results[key] = r
+            return self._results_map(results)
+        cm_name, cm = _cm_member(self.inner) if lin is None and cr is None else (None, None)
+        cm_out = _cm_check_independent(cm, history) if cm is not None else None
+        if cm_out is not None:
+            cm_res, unknown = cm_out
+            subs = subhistories(history, list(cm_res) if cm_name is not None else unknown)
+            for key in unknown:
+                # an :f the model has no clause for: the per-key path, where check_safe keeps what the key raises
+                cm_res[key] = check_safe(cm, test, subs[key], {"subdirectory": [DIR, key], "history-key": key})
+            if cm_name is None:
+                return self._results_map(cm_res)
+            results = {}
+            for key, res in cm_res.items():
+                r = {}
+                for nm, c in self.inner.checker_map.items():
+                    r[nm] = res if nm == cm_name else check_safe(
                         c, test, subs[key], {"subdirectory": [DIR, key], "history-key": key})
                 r["valid?"] = merge_valid(x.get("valid?") if isinstance(x, dict) else None for x in r.values())
                 results[key] = r

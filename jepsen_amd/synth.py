@@ -1027,3 +1027,152 @@ def monotonic_columns_to_ops(cols):
         out.append({"process": p if p >= 0 else "nemesis", "type": ("invoke", "ok", "fail", "info")[int(cols.type[i])],
                     "f": names[fi] if 0 <= fi < len(names) else "read", "value": v})
     return out
+
+
+# ---------------------------------------------------------------------------
+# causal workload, jepsen/src/jepsen/tests/causal.clj:118-130
+CAUSAL_VIOLATIONS = ("stale-read", "broken-link", "skipped-write", "read-init")
+
+
+def causal_history(n_keys=64, violations=0, seed=0, p_info=0.02, concurrent=8, n_procs=None):
+    """A keyed causal history as Columns in the causal encoding (include/jh.h:
+    aux = a (position, link) pair per row; key ids 0 .. n_keys - 1, `keys` the
+    same numbers). Every key has one thread and the five ops [ri cw1 r cw2 r],
+    an invocation and a completion each; about 2 * `concurrent` keys are in
+    flight at a time and their rows interleave. An :ok completion takes the next
+    value of a global increasing position and links to the key's previous
+    position, the first to :init. With p_info a completion is :info instead, and
+    the key's later ops :fail (its :ok ops stay a valid prefix). violations:
+    that many distinct keys, complete ones, get one fault each, the kinds of
+    CAUSAL_VIOLATIONS in turn: the last read returns the first write, a link
+    names another position, the first write writes 2, the read-init returns 7."""
+    from . import _abi as A
+    rng = np.random.default_rng(seed)
+    K, OPS = int(n_keys), 5
+    n_procs = int(n_procs or concurrent)
+    stop = np.where(rng.random((K, OPS)) < p_info, np.arange(OPS), OPS).min(axis=1)     # the first op that is not :ok
+    bad = rng.choice(K, size=min(int(violations), K), replace=False) if violations else np.zeros(0, np.int64)
+    stop[bad] = OPS
+    f_op = np.asarray([A.F_READ_INIT, A.F_WRITE, A.F_READ, A.F_WRITE, A.F_READ], np.int64)
+    v_inv = np.asarray([A.NIL, 1, A.NIL, 2, A.NIL], np.int64)
+    v_ok = np.tile(np.asarray([0, 1, 1, 2, 2], np.int64), (K, 1))
+    kinds = np.arange(len(bad)) % len(CAUSAL_VIOLATIONS)
+    v_ok[bad[kinds == 0], 4] = 1
+    v_ok[bad[kinds == 2], 1] = 2
+    v_ok[bad[kinds == 3], 0] = 7
+    op_idx = np.arange(OPS)[None, :]
+    ctype = np.where(op_idx < stop[:, None], A.TYPE_OK, np.where(op_idx == stop[:, None], A.TYPE_INFO, A.TYPE_FAIL))
+    # rows: (key, op, half) -> a time; a key's ten rows keep their order
+    t = (np.arange(K)[:, None] // max(int(concurrent), 1) * 1.0 + rng.random((K, 1))) * 10 \
+        + np.arange(2 * OPS)[None, :] + rng.random((K, 2 * OPS))
+    t = np.sort(t, axis=1)
+    order = np.argsort(t.ravel(), kind="stable")
+    n = K * 2 * OPS
+    row_of = np.empty(n, np.int64)
+    row_of[order] = np.arange(n)
+    row_of = row_of.reshape(K, OPS, 2)
+    typ = np.empty(n, np.int64)
+    f = np.empty(n, np.int64)
+    key = np.empty(n, np.int64)
+    val = np.full(n, A.NIL, np.int64)
+    aux = np.full(2 * n, A.NIL, np.int64)
+    kk = np.repeat(np.arange(K), OPS).reshape(K, OPS)
+    for half in (0, 1):
+        r = row_of[:, :, half]
+        f[r] = f_op[None, :]
+        key[r] = kk
+        typ[r] = A.TYPE_INVOKE if half == 0 else ctype
+    val[row_of[:, :, 0]] = v_inv[None, :]
+    comp = row_of[:, :, 1]
+    val[comp] = np.where(ctype == A.TYPE_OK, v_ok, v_inv[None, :])
+    pos = comp + 1                                            # global and increasing along the history
+    link = np.concatenate([np.full((K, 1), A.CAUSAL_INIT, np.int64), pos[:, :-1]], axis=1)
+    which = 1 + rng.integers(OPS - 1, size=len(bad))
+    sel = kinds == 1
+    link[bad[sel], which[sel]] += 1 + 2 * n                   # no row has this position
+    okm = ctype == A.TYPE_OK
+    aux[2 * comp[okm]] = pos[okm]
+    aux[2 * comp[okm] + 1] = link[okm]
+    return Columns(n=n, process=key % n_procs, type=typ, f=f, key=key, value=val, value2=np.zeros(n, np.int64), n_keys=K,
+                   aux=aux, keys=list(range(K)))
+
+
+def causal_columns_to_ops(cols):
+    """Op maps of a causal history's Columns (independent tuples for keyed
+    rows; jepsen_amd/causal.py decode)."""
+    from . import causal
+    return causal.decode(cols)
+
+
+# ---------------------------------------------------------------------------
+# Adya G2 workload, jepsen/src/jepsen/tests/adya.clj:12-60
+def g2_history(n_keys=64, illegal=0, seed=0, p_ok=0.5, p_info=0.1, concurrent=8, nemesis_every=1000):
+    """A G2 history as Columns in the G2 encoding (include/jh.h): every key has
+    two :insert ops on two threads, [key [nil b-id]] and [key [a-id nil]] with
+    globally unique ids (value = the id, value2 = 0 for the first form and 1 for
+    the second), an invocation and a completion each, about 2 * `concurrent`
+    keys in flight at a time. Each completion is :ok, :fail or :info; only the
+    `illegal` keys (distinct, random) have both :ok. A :nemesis :info row stands
+    after every `nemesis_every` rows. Key ids 0 .. n_keys - 1 in order of first
+    appearance are the keys themselves."""
+    from . import _abi as A
+    rng = np.random.default_rng(seed)
+    K = int(n_keys)
+    first_ok = rng.random(K) < p_ok
+    second_ok = ~first_ok & (rng.random(K) < p_ok)
+    ill = rng.choice(K, size=min(int(illegal), K), replace=False) if illegal else np.zeros(0, np.int64)
+    first_ok[ill] = True
+    second_ok[ill] = True
+    oks = np.stack([first_ok, second_ok], axis=1)
+    ctype = np.where(oks, A.TYPE_OK, np.where(rng.random((K, 2)) < p_info, A.TYPE_INFO, A.TYPE_FAIL))
+    t_inv = (np.arange(K)[:, None] // max(int(concurrent), 1) * 1.0 + rng.random((K, 1))) * 4 + rng.random((K, 2))
+    t = np.stack([t_inv, t_inv + 0.01 + 2 * rng.random((K, 2))], axis=2)       # (key, insert, invoke / completion)
+    order = np.argsort(t.ravel(), kind="stable")
+    m = 4 * K
+    rank = np.empty(m, np.int64)
+    rank[order] = np.arange(m)
+    every = max(int(nemesis_every), 1)
+    row_of = (rank + rank // every).reshape(K, 2, 2)          # a nemesis row after every `every` rows
+    n = m + m // every
+    typ = np.full(n, A.TYPE_INFO, np.int64)
+    f = np.full(n, A.F_FIRST_INTERNED, np.int64)
+    key = np.full(n, -1, np.int64)
+    proc = np.full(n, -1, np.int64)
+    val = np.full(n, A.NIL, np.int64)
+    val2 = np.zeros(n, np.int64)
+    ids = 1 + np.arange(2 * K).reshape(K, 2)
+    # key ids in order of first appearance
+    firsts = row_of.reshape(K, 4).min(axis=1)
+    kid = np.empty(K, np.int64)
+    kid[np.argsort(firsts, kind="stable")] = np.arange(K)
+    for half in (0, 1):
+        r = row_of[:, :, half]
+        f[r] = A.F_INSERT
+        key[r] = kid[:, None]
+        proc[r] = 2 * (np.arange(K)[:, None] % max(int(concurrent), 1)) + np.arange(2)[None, :]
+        typ[r] = A.TYPE_INVOKE if half == 0 else ctype
+        val[r] = ids
+        val2[r] = np.arange(2)[None, :]
+    return Columns(n=n, process=proc, type=typ, f=f, key=key, value=val, value2=val2, n_keys=K, aux=np.zeros(1, np.int64),
+                   keys=list(range(K)), f_names=["start"])
+
+
+def g2_columns_to_ops(cols):
+    """Op maps of a G2 history's Columns: an insert's :value is the independent
+    tuple [key [nil id]] or [key [id nil]]."""
+    from . import _abi as A
+    from .history import TYPE_NAMES, tuple_
+    out = []
+    for i in range(cols.n):
+        p = int(cols.process[i])
+        op = {"process": p if p >= 0 else "nemesis", "type": TYPE_NAMES[int(cols.type[i])]}
+        if int(cols.f[i]) == A.F_INSERT:
+            v = int(cols.value[i])
+            op["f"] = "insert"
+            op["value"] = tuple_(cols.keys[int(cols.key[i])], [v, None] if int(cols.value2[i]) else [None, v])
+        else:
+            j = int(cols.f[i]) - A.F_FIRST_INTERNED
+            op["f"] = cols.f_names[j] if 0 <= j < len(cols.f_names) else "start"
+            op["value"] = None
+        out.append(op)
+    return out
