@@ -34,6 +34,10 @@
  *   jh_check_cycle            <- (jepsen.tests.cycle/checker (cycle/combine ...))
  *                                                   jepsen/src/jepsen/tests/cycle.clj:202-216,911-934
  *   jh_scc                    <- cycle/tarjan       jepsen/src/jepsen/tests/cycle.clj:150-160
+ *   jh_perf                   <- (checker/perf), (checker/latency-graph), (checker/rate-graph):
+ *                                 the reduction behind the three plots
+ *                                                   jepsen/src/jepsen/checker.clj:736-768
+ *                                                   jepsen/src/jepsen/checker/perf.clj
  *
  * Plain pointers and sizes only. The caller owns every buffer; the library
  * never retains a caller pointer after returning. All entry points are
@@ -1174,6 +1178,74 @@ typedef struct jh_g2_result {
 
 int jh_check_g2(jh_ctx *ctx, const jh_history *h, const jh_g2_opts *opts, jh_g2_result *res,
                 int64_t *illegal_out, int64_t illegal_cap, char *err, size_t errlen);
+
+/* (checker/latency-graph), (checker/rate-graph) and (checker/perf),
+ * checker.clj:736-768 over checker/perf.clj and util.clj:606-640 (additive to
+ * ABI 8: new structs and one symbol). The product of these checkers is the plot,
+ * not :valid?; jh_perf is the reduction over the history that the three plots
+ * need, all of it in integers. The caller turns the outputs into the series of
+ * perf/plot!.
+ *
+ * Only process, type and f of the history are read, and `time`, the :time
+ * column (nanoseconds, indexed by row, host or device like the history).
+ *
+ * Pairing (util/history->latencies): rows are put in per-process order, a
+ * stable sort by process (every value a key of its own, negative ones included).
+ * A non-invoke row pairs with the row just before it in that order exactly when
+ * that row is an invoke; every other row is unpaired. The latency of a pair is
+ * time[completion] - time[invoke], signed.
+ *   pair     [n] the partner row of each row, or -1
+ *   t_max    max(0, every row's time)
+ * Raw points (perf/point-graph!): the paired invokes, stably partitioned by
+ * (f ascending; completion type in the order :ok :info :fail; row ascending).
+ *   pt_row   [n_paired] the invoke rows in that order
+ *   series   [n_series][3] = f, completion type, count: the non-empty series
+ * Quantile groups (perf/quantiles-graph!), only when n_unpaired_invokes == 0
+ * (has_quantiles; the reference throws otherwise): every invoke by (f, bucket of
+ * the invoke's time with dt_quantiles).
+ *   groups   [n_groups][7] = f, bucket, count, and the latency (ns) at 0.5, 0.95,
+ *            0.99 and 1: sorted[min(count - 1, (int64)floor((double)count * q))];
+ *            in (f, bucket) order
+ * Rate cells (perf/rate-graph!): the non-invoke rows with process >= 0.
+ *   cells    [n_cells][4] = f, type, bucket with dt_rate, count; in (f, type
+ *            code, bucket) order
+ * The bucket of a time t is (int64)(((double)t / 1e9) / (double)dt): the
+ * reference's two double divisions, then truncation.
+ *
+ * Any output pointer may be NULL. A list with fewer than its count entries of
+ * room (its cap) receives the prefix; the counts are those of the whole result.
+ * n = 0 is JH_OK with every count 0. The pairing counts are filled when
+ * JH_PERF_PAIR, _POINTS or _QUANTILES is wanted; t_max always.
+ *
+ * JH_EUNSUPPORTED (the shim falls back): a JH_NIL or negative time; an f code
+ * outside [0, f_count); f_count above 2^20; more than 2^31 - 2 rows.
+ * JH_EINVAL: f_count < 1, a negative dt, a want bit that is not defined. */
+#define JH_PERF_PAIR      1
+#define JH_PERF_POINTS    2
+#define JH_PERF_QUANTILES 4
+#define JH_PERF_RATE      8
+#define JH_PERF_ALL       15
+
+typedef struct jh_perf_opts {
+    int64_t f_count;             /* f codes lie in [0, f_count): 16 + the interned f */
+    int64_t dt_quantiles;        /* seconds; 0 = 30 */
+    int64_t dt_rate;             /* seconds; 0 = 10 */
+    int32_t want, pad;           /* JH_PERF_* bits; 0 = JH_PERF_ALL */
+    int64_t reserved[4];
+} jh_perf_opts;
+
+typedef struct jh_perf_result {
+    int64_t n_invokes, n_paired, n_unpaired_invokes;
+    int64_t first_unpaired_invoke;   /* a row, or -1 */
+    int64_t t_max;
+    int64_t n_series, n_groups, n_cells;
+    int32_t has_quantiles, pad;      /* 1: the groups were produced */
+    double device_ms;
+} jh_perf_result;
+
+int jh_perf(jh_ctx *ctx, const jh_history *h, const int64_t *time, const jh_perf_opts *opts, jh_perf_result *res,
+            int64_t *pair, int64_t pair_cap, int64_t *pt_row, int64_t pt_cap, int64_t *series, int64_t series_cap,
+            int64_t *groups, int64_t group_cap, int64_t *cells, int64_t cell_cap, char *err, size_t errlen);
 
 #ifdef __cplusplus
 }

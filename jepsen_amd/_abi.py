@@ -309,6 +309,26 @@ class JhG2Result(C.Structure):
                 ("device_ms", C.c_double)]
 
 
+# checker/perf: jh_perf (additive to ABI 8)
+PERF_PAIR, PERF_POINTS, PERF_QUANTILES, PERF_RATE, PERF_ALL = 1, 2, 4, 8, 15   # JH_PERF_*
+PERF_TILE = 1024              # sorted slots per tile of jh_perf.hip's pairing kernel (the tests straddle its edges)
+PERF_DT_QUANTILES, PERF_DT_RATE = 30, 10      # perf.clj:505, :549
+PERF_QS = (0.5, 0.95, 0.99, 1.0)              # the picks of a jh_perf group record, words 3..6
+PERF_TYPE_ORDER = (TYPE_OK, TYPE_INFO, TYPE_FAIL)   # perf.clj:173-175
+
+
+class JhPerfOpts(C.Structure):
+    _fields_ = [("f_count", C.c_int64), ("dt_quantiles", C.c_int64), ("dt_rate", C.c_int64),
+                ("want", C.c_int32), ("pad", C.c_int32), ("reserved", C.c_int64 * 4)]
+
+
+class JhPerfResult(C.Structure):
+    _fields_ = [("n_invokes", C.c_int64), ("n_paired", C.c_int64), ("n_unpaired_invokes", C.c_int64),
+                ("first_unpaired_invoke", C.c_int64), ("t_max", C.c_int64),
+                ("n_series", C.c_int64), ("n_groups", C.c_int64), ("n_cells", C.c_int64),
+                ("has_quantiles", C.c_int32), ("pad", C.c_int32), ("device_ms", C.c_double)]
+
+
 class JhCycleOpts(C.Structure):
     _fields_ = [("analyzers", C.c_int32), ("path", C.c_int32), ("extra_src", _p64), ("extra_dst", _p64),
                 ("n_extra", C.c_int64), ("reserved", C.c_int64 * 4)]

@@ -82,6 +82,9 @@ def lib():
                                           C.POINTER(A.JhCausalKey), C.c_char_p, C.c_size_t]
             L.jh_check_g2.argtypes = [C.c_void_p, H, C.POINTER(A.JhG2Opts), C.POINTER(A.JhG2Result), p64, C.c_int64,
                                       C.c_char_p, C.c_size_t]
+            L.jh_perf.argtypes = [C.c_void_p, H, p64, C.POINTER(A.JhPerfOpts), C.POINTER(A.JhPerfResult),
+                                  p64, C.c_int64, p64, C.c_int64, p64, C.c_int64, p64, C.c_int64, p64, C.c_int64,
+                                  C.c_char_p, C.c_size_t]
             L.jh_scc.argtypes = [C.c_void_p, C.c_int64, p64, p64, C.c_int64, C.POINTER(A.JhCycleOpts),
                                  C.POINTER(A.JhCycleResult), p64, p64, p64, C.c_int64, C.c_int64, C.c_char_p, C.c_size_t]
             L.jh_check_cycle.argtypes = [C.c_void_p, H, C.POINTER(A.JhCycleOpts), C.POINTER(A.JhCycleResult), p64, p64,
@@ -120,7 +123,7 @@ EXPORTED_SYMBOLS = ["jh_version", "jh_open", "jh_open_multi", "jh_open_devices",
                     "jh_check_cas", "jh_check_cas_independent_device", "jh_lin_configs", "jh_check_counter",
                     "jh_check_set", "jh_check_set_bitmaps", "jh_check_set_full", "jh_check_set_full_opts", "jh_check_total_queue", "jh_check_queue",
                     "jh_check_unique_ids", "jh_check_bank", "jh_check_long_fork", "jh_check_causal_reverse",
-                    "jh_check_causal", "jh_check_g2",
+                    "jh_check_causal", "jh_check_g2", "jh_perf",
                     "jh_scc", "jh_check_cycle",
                     "jh_host_alloc", "jh_host_free",
                     # include/jh_io.h
@@ -568,6 +571,57 @@ class Context:
         _raise(rc, err)
         res = {name: getattr(r, name) for name, _ in A.JhG2Result._fields_}
         res["illegal"] = (pairs[:2 * min(r.illegal_count, cap)] if cap else np.zeros(0, np.int64)).reshape(-1, 2)
+        return res
+
+    # -- perf -----------------------------------------------------------------
+    def perf(self, cols, time, on_device=False, want=A.PERF_ALL, f_count=None, dt_quantiles=0, dt_rate=0,
+             pair_cap=None, pt_cap=None, series_cap=None, group_cap=None, cell_cap=None):
+        """jh_perf: the result fields plus numpy arrays `pair` (per row the
+        partner row or -1), `pt_row` (the paired invokes in series order),
+        `series` (k, 3: f, completion type, count), `groups` (k, 7: f, bucket,
+        count, latency at 0.5 / 0.95 / 0.99 / 1) and `cells` (k, 4: f, type,
+        bucket, count). `time`: the :time column (numpy int64, or a device
+        pointer when on_device). A cap of None asks for the whole list (a second
+        call when the first guess was too small); a list that is not wanted is
+        empty. f_count: default 16 + the interned f of cols."""
+        h = A.make_history(cols, on_device=on_device)
+        n = int(cols.n)
+        want = int(want) or A.PERF_ALL
+        if f_count is None:
+            f_count = A.F_FIRST_INTERNED + len(getattr(cols, "f_names", None) or [])
+        o = A.JhPerfOpts(f_count=int(f_count), dt_quantiles=int(dt_quantiles), dt_rate=int(dt_rate), want=want)
+        if on_device:
+            tp = C.cast(C.c_void_p(int(time)), C.POINTER(C.c_int64))
+        else:
+            t_host = np.ascontiguousarray(time, np.int64) if n else np.zeros(1, np.int64)   # held until the call returns
+            tp = A.ptr64(t_host)
+        guess = {"pair": n, "pt_row": n // 2 + 1, "series": 64, "groups": 1024, "cells": 1024}
+        caps = {"pair": pair_cap, "pt_row": pt_cap, "series": series_cap, "groups": group_cap, "cells": cell_cap}
+        width = {"pair": 1, "pt_row": 1, "series": 3, "groups": 7, "cells": 4}
+        wanted = {"pair": want & A.PERF_PAIR, "pt_row": want & A.PERF_POINTS, "series": want & A.PERF_POINTS,
+                  "groups": want & A.PERF_QUANTILES, "cells": want & A.PERF_RATE}
+        count_of = {"pair": lambda r: n if wanted["pair"] else 0, "pt_row": lambda r: r.n_paired if wanted["pt_row"] else 0,
+                    "series": lambda r: r.n_series, "groups": lambda r: r.n_groups, "cells": lambda r: r.n_cells}
+        cur = {k: (guess[k] if caps[k] is None else max(int(caps[k]), 0)) if wanted[k] else 0 for k in caps}
+        r = A.JhPerfResult()
+        err = C.create_string_buffer(1024)
+        for _ in range(2):
+            bufs = {k: np.zeros(width[k] * cur[k], np.int64) if cur[k] else None for k in cur}
+            args = []
+            for k in ("pair", "pt_row", "series", "groups", "cells"):
+                args += [A.ptr64(bufs[k]), cur[k]]
+            rc = lib().jh_perf(self._h, C.byref(h), tp, C.byref(o), C.byref(r), *args, err, len(err))
+            _raise(rc, err)
+            short = [k for k in cur if caps[k] is None and wanted[k] and count_of[k](r) > cur[k]]
+            if not short:
+                break
+            for k in short:
+                cur[k] = int(count_of[k](r))
+        res = {name: getattr(r, name) for name, _ in A.JhPerfResult._fields_ if name != "pad"}
+        for k in cur:
+            kk = min(int(count_of[k](r)), cur[k])
+            a = bufs[k][:width[k] * kk] if bufs[k] is not None else np.zeros(0, np.int64)
+            res[k] = a.reshape(-1, width[k]) if width[k] > 1 else a
         return res
 
     # -- cycle ----------------------------------------------------------------

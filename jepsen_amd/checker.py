@@ -679,6 +679,94 @@ def unique_ids(path=0, dup_cap=A.UID_DUP_CAP):
     return UniqueIds(path, dup_cap)
 
 
+class _PerfChecker(Checker):
+    """Shared by latency-graph and rate-graph: options merge as (merge opts
+    c-opts), the history goes through jh_perf when it can (perf.device_reduction)
+    and through the literal host path otherwise, and the plot maps stay on the
+    checker as `last_plots` (name -> map) next to {:valid? true}. force_host:
+    the host path whatever the history is (tests, comparisons)."""
+    want = 0
+
+    def __init__(self, opts=None, force_host=False):
+        self.opts = dict(opts or {})
+        self.force_host = force_host
+        self.last_plots = {}
+        self.last_path = None
+
+    def _reduce(self, history):
+        from . import perf
+        self.last_path = "host"
+        if self.force_host:
+            return None
+        red = perf.device_reduction(_ctx(), history, self.want)
+        if red is not None:
+            self.last_path = "device"
+        return red
+
+    @staticmethod
+    def _ops(history):
+        if isinstance(history, H.Columns):
+            raise ValueError("the host path of perf needs op maps")
+        return list(history)
+
+
+class LatencyGraph(_PerfChecker):
+    """(checker/latency-graph), checker.clj:736-747: the raw latency points,
+    then the quantiles. With an unpaired invoke the raw plot is built and
+    written and quantiles-graph! then throws (a NullPointerException out of
+    latency-point in the reference, a TypeError here)."""
+    want = A.PERF_PAIR | A.PERF_POINTS | A.PERF_QUANTILES
+
+    def check(self, test, history, c_opts):
+        from . import perf
+        o = dict(self.opts, **(c_opts or {}))
+        self.last_plots = {}
+        red = self._reduce(history)
+        if red is None:
+            ops = self._ops(history)
+            self.last_plots["latency-raw"] = raw = perf.point_graph(test, ops, o)
+            perf.plot(test, raw, o, "latency-raw")
+            self.last_plots["latency-quantiles"] = qs = perf.quantiles_graph(test, ops, o)
+            perf.plot(test, qs, o, "latency-quantiles")
+            return {"valid?": True}
+        self.last_plots["latency-raw"] = raw = perf.point_graph_from_device(test, red, o)
+        perf.plot(test, raw, o, "latency-raw")
+        if red.raw["n_unpaired_invokes"]:
+            raise TypeError(f"latency-point: the invocation at index {red.raw['first_unpaired_invoke']} has no "
+                            ":latency (NullPointerException)")
+        self.last_plots["latency-quantiles"] = qs = perf.quantiles_graph_from_device(test, red, o)
+        perf.plot(test, qs, o, "latency-quantiles")
+        return {"valid?": True}
+
+
+class RateGraph(_PerfChecker):
+    """(checker/rate-graph), checker.clj:749-759."""
+    want = A.PERF_RATE
+
+    def check(self, test, history, c_opts):
+        from . import perf
+        o = dict(self.opts, **(c_opts or {}))
+        self.last_plots = {}
+        red = self._reduce(history)
+        p = perf.rate_graph(test, self._ops(history), o) if red is None else perf.rate_graph_from_device(test, red, o)
+        self.last_plots["rate"] = p
+        perf.plot(test, p, o, "rate")
+        return {"valid?": True}
+
+
+def latency_graph(opts=None, force_host=False):
+    return LatencyGraph(opts, force_host)
+
+
+def rate_graph(opts=None, force_host=False):
+    return RateGraph(opts, force_host)
+
+
+def perf(opts=None, force_host=False):
+    """(checker/perf), checker.clj:761-768."""
+    return compose({"latency-graph": latency_graph(opts, force_host), "rate-graph": rate_graph(opts, force_host)})
+
+
 # jepsen.tests.bank lives in its own namespace (tests/bank.clj); its checker is
 # reached as checker.bank.checker(opts), next to the names above
 from . import bank  # noqa: E402,F401

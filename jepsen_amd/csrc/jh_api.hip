@@ -595,6 +595,38 @@ int jh_check_g2(jh_ctx *ctx, const jh_history *h, const jh_g2_opts *opts, jh_g2_
     });
 }
 
+int jh_perf(jh_ctx *ctx, const jh_history *h, const int64_t *time, const jh_perf_opts *opts, jh_perf_result *res,
+            int64_t *pair, int64_t pair_cap, int64_t *pt_row, int64_t pt_cap, int64_t *series, int64_t series_cap,
+            int64_t *groups, int64_t group_cap, int64_t *cells, int64_t cell_cap, char *err, size_t errlen) {
+    if (!ctx || !res || !opts) { set_err(err, errlen, "null argument"); return JH_EINVAL; }
+    if (opts->f_count < 1) { set_err(err, errlen, "perf: f_count < 1"); return JH_EINVAL; }
+    if (opts->dt_quantiles < 0 || opts->dt_rate < 0) { set_err(err, errlen, "perf: a negative dt"); return JH_EINVAL; }
+    if (opts->want & ~JH_PERF_ALL) { set_err(err, errlen, "perf: an undefined want bit"); return JH_EINVAL; }
+    ctx = primary(ctx);
+    std::lock_guard<std::mutex> g(ctx->mu);
+    return guarded(err, errlen, [&] {
+        if (!h) throw_jh(JH_EINVAL, "null history");
+        if (h->n < 0) throw_jh(JH_EINVAL, "negative entry count");
+        if (h->n > 0 && (!h->process || !h->type || !h->f)) throw_jh(JH_EINVAL, "missing history column");
+        if (h->n > 0 && !time) throw_jh(JH_EINVAL, "perf needs the :time column");
+        HIP_TRY(hipSetDevice(ctx->device));
+        // only the three columns the reduction reads are staged
+        jh_history d = *h;
+        const int64_t *dt = time;
+        if (!h->on_device) {
+            d.process = stage_col(ctx, WS_COL_PROCESS, h->process, h->n, ctx->stream);
+            d.type = stage_col(ctx, WS_COL_TYPE, h->type, h->n, ctx->stream);
+            d.f = stage_col(ctx, WS_COL_F, h->f, h->n, ctx->stream);
+            dt = stage_col(ctx, WS_PF_TIME, time, h->n, ctx->stream);
+            d.on_device = 1;
+        }
+        const auto cap = [](int64_t c) { return c < 0 ? (int64_t)0 : c; };
+        const PerfOut out = {pair, cap(pair_cap), pt_row, cap(pt_cap), series, cap(series_cap),
+                             groups, cap(group_cap), cells, cap(cell_cap)};
+        perf_reduce(ctx, &d, dt, opts, res, out, ctx->stream);
+    });
+}
+
 int jh_scc(jh_ctx *ctx, int64_t n_vertices, const int64_t *src, const int64_t *dst, int64_t n_edges,
            const jh_cycle_opts *opts, jh_cycle_result *res, int64_t *labels_out, int64_t *scc_off, int64_t *scc_rows,
            int64_t scc_cap, int64_t rows_cap, char *err, size_t errlen) {

@@ -138,6 +138,8 @@ enum WsSlot {
     WS_BFS_TAKEN,
     WS_CM_META, WS_CM_WORDS, WS_CM_TCNT, WS_CM_TBASE, WS_CM_TMP, WS_CM_KEY, WS_CM_ROW, WS_CM_OFF, WS_CM_SUM, WS_CM_EV, WS_CM_OUT,
     WS_G2_META, WS_G2_CNT, WS_G2_WORDS, WS_G2_TCNT, WS_G2_TBASE, WS_G2_TMP, WS_G2_MIN, WS_G2_OUT,
+    WS_PF_META, WS_PF_TIME, WS_PF_TMP, WS_PF_K64A, WS_PF_K64B, WS_PF_K64C, WS_PF_K64D, WS_PF_V32A, WS_PF_V32B,
+    WS_PF_K32A, WS_PF_K32B, WS_PF_PAIR, WS_PF_RUN_U, WS_PF_RUN_C, WS_PF_RUN_S, WS_PF_NRUNS, WS_PF_OUT,
     WS_COUNT
 };
 
@@ -236,6 +238,12 @@ void causal_check(jh_ctx *ctx, const jh_history *dh, jh_causal_result *res, jh_c
 // adya g2 (jh_g2.hip); illegal_out = [key id, count] pairs
 void g2_check(jh_ctx *ctx, const jh_history *dh, jh_g2_result *res, int64_t *illegal_out, int64_t illegal_cap,
               hipStream_t stream);
+// perf (jh_perf.hip); dh's process / type / f and time_dev are device columns, the outputs host buffers (any may be null)
+struct PerfOut {
+    int64_t *pair, pair_cap, *pt_row, pt_cap, *series, series_cap, *groups, group_cap, *cells, cell_cap;
+};
+void perf_reduce(jh_ctx *ctx, const jh_history *dh, const int64_t *time_dev, const jh_perf_opts *opts,
+                 jh_perf_result *res, const PerfOut &out, hipStream_t stream);
 // cycle (jh_cycle.hip); src / dst are host edge lists, the outputs host buffers (any may be null)
 struct CycleOut {
     int64_t *labels, *scc_off, *scc_rows, scc_cap, rows_cap, *edges, edge_cap;

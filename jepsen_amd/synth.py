@@ -1176,3 +1176,75 @@ def g2_columns_to_ops(cols):
             op["value"] = None
         out.append(op)
     return out
+
+
+def perf_history(n=4096, procs=5, fs=("read", "write", "cas"), seed=0, p_fail=0.1, p_info=0.05, nemesis_every=1000,
+                 dangling=False, mean_latency_ms=20.0, mean_think_ms=5.0):
+    """A history for checker/perf as Columns with a `time` attribute (integer
+    nanoseconds): about n rows of paired client ops on `procs` processes, each
+    process's times increasing, the f drawn from `fs`, a share of :fail and
+    :info completions; after every `nemesis_every` client rows a :nemesis :info
+    pair, :start and :stop in turn (the two rows of a pair carry their
+    neighbour's time). dangling: the last op of the last process never
+    completes (an unpaired invoke). Only process, type, f and time mean
+    anything; key, value and value2 are zeros."""
+    from . import _abi as A
+    from .history import KNOWN_F, Columns
+    rng = np.random.default_rng(seed)
+    P, n_ops = max(int(procs), 1), max(int(n) // 2, 0)
+    names, code = [], {}
+    for f in list(fs) + ["start", "stop"]:
+        if f in KNOWN_F:
+            code[f] = KNOWN_F[f]
+        elif f not in code:
+            code[f] = A.F_FIRST_INTERNED + len(names)
+            names.append(f)
+    op_p = np.arange(n_ops) % P
+    lat = 1 + rng.exponential(mean_latency_ms * 1e6, n_ops).astype(np.int64)
+    think = 1 + rng.exponential(mean_think_ms * 1e6, n_ops).astype(np.int64)
+    t_inv = np.zeros(n_ops, np.int64)
+    for p in range(P):                                        # a process's ops follow one another
+        sel = np.nonzero(op_p == p)[0]
+        t_inv[sel] = np.cumsum(think[sel] + np.concatenate(([0], lat[sel][:-1])))
+    u = rng.random(n_ops)
+    ctype = np.where(u < p_fail, A.TYPE_FAIL, np.where(u < p_fail + p_info, A.TYPE_INFO, A.TYPE_OK))
+    f_op = np.asarray([code[f] for f in fs], np.int64)[rng.integers(0, len(fs), n_ops)] if n_ops else np.zeros(0, np.int64)
+    t = np.concatenate([t_inv, t_inv + lat])
+    typ = np.concatenate([np.full(n_ops, A.TYPE_INVOKE), ctype])
+    proc = np.concatenate([op_p, op_p])
+    f = np.concatenate([f_op, f_op])
+    keep = np.ones(2 * n_ops, bool)
+    if dangling and n_ops:
+        keep[n_ops + np.nonzero(op_p == P - 1)[0][-1]] = False
+    order = np.argsort(t, kind="stable")
+    order = order[keep[order]]
+    t, typ, proc, f = t[order], typ[order], proc[order], f[order]
+    every = max(int(nemesis_every), 1)
+    cuts = np.arange(every, len(t) + 1, every)                # a nemesis pair after these many client rows
+    if len(cuts):
+        at = np.repeat(cuts, 2)
+        nf = np.repeat(np.where(np.arange(len(cuts)) % 2 == 0, code["start"], code["stop"]), 2)
+        t = np.insert(t, at, t[at - 1])
+        typ = np.insert(typ, at, A.TYPE_INFO)
+        proc = np.insert(proc, at, -1)
+        f = np.insert(f, at, nf)
+    m = len(t)
+    z = np.zeros(m, np.int64)
+    cols = Columns(n=m, process=proc.astype(np.int64), type=typ.astype(np.int64), f=f.astype(np.int64), key=z, value=z,
+                   value2=z, n_keys=0, aux=np.zeros(1, np.int64), f_names=names)
+    cols.time = t.astype(np.int64)
+    return cols
+
+
+def perf_columns_to_ops(cols):
+    """Op maps (process, type, f, time, index) of a perf history's Columns."""
+    from . import _abi as A
+    from .history import KNOWN_F, TYPE_NAMES
+    known = {v: k for k, v in KNOWN_F.items()}
+    out = []
+    for i in range(cols.n):
+        p, c = int(cols.process[i]), int(cols.f[i])
+        out.append({"process": p if p >= 0 else "nemesis", "type": TYPE_NAMES[int(cols.type[i])],
+                    "f": known[c] if c in known else cols.f_names[c - A.F_FIRST_INTERNED], "time": int(cols.time[i]),
+                    "index": i})
+    return out
