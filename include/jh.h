@@ -27,6 +27,9 @@
  *                                                   jepsen/src/jepsen/tests/long_fork.clj:158-324
  *   jh_check_causal_reverse   <- (independent/checker (jepsen.tests.causal-reverse/checker))
  *                                                   jepsen/src/jepsen/tests/causal_reverse.clj:21-84
+ *   jh_check_set_independent  <- (independent/checker (checker/set))
+ *                                                   jepsen/src/jepsen/independent.clj:247-298
+ *                                                   jepsen/src/jepsen/checker.clj:182-233
  *   jh_check_causal           <- (independent/checker (jepsen.tests.causal/check (causal-register)))
  *                                                   jepsen/src/jepsen/tests/causal.clj:33-110
  *   jh_check_g2               <- (jepsen.tests.adya/g2-checker)
@@ -882,6 +885,79 @@ typedef struct jh_causal_reverse_result {
 int jh_check_causal_reverse(jh_ctx *ctx, const jh_history *h, const jh_causal_reverse_opts *opts,
                             jh_causal_reverse_result *res, int32_t *key_valid, int64_t *errors_out, int64_t err_cap,
                             int64_t *missing_out, int64_t missing_cap, char *err, size_t errlen);
+
+/* (independent/checker (checker/set)), independent.clj:247-298 over
+ * checker.clj:182-233 (additive to ABI 8: new structs and one new symbol),
+ * batched over the keys of an independent history: every key is judged as
+ * jh_check_set_bitmaps judges its sub-history, in one call.
+ *
+ * The standard columns, with `key` as in jh_check_cas_independent and set reads
+ * in aux through value / value2. Key k's sub-history is its own rows plus the
+ * un-keyed rows (independent.clj:234-245); the call takes a keyed history only
+ * when no un-keyed row can matter (below). Per key: attempts = the elements of
+ * its :invoke :add rows, adds = those of its :ok :add rows (any process), the
+ * final read R = the elements of its LAST :ok :read row (repeated elements
+ * count once; an empty read is a read). No such row, or a nil :value there, is
+ * JH_UNKNOWN / JH_CAUSE_NIL_VALUE ("Set was never read"). ok = R n attempts,
+ * unexpected = R - attempts, lost = adds - R, recovered = ok - adds; valid iff
+ * lost and unexpected are empty. Adds after the final read count.
+ * first_fail_entry is the smallest row of an :ok :add of the key whose element
+ * is lost, else the key's final-read row if anything is unexpected, else -1.
+ *
+ * keys_out (may be NULL) receives max(n_keys, 1) records. A key's four result
+ * sets are bitmaps over [base, base + 32 n_words), base = the smallest element
+ * of its add rows and its final read (0 when it has none), at words
+ * [word_off, word_off + n_words) of ok / lost / unexpected / recovered: each
+ * key owns a whole number of words, no two keys share one, and word_off is the
+ * running sum of n_words in key order. A JH_UNKNOWN key and a key in no row
+ * (rows == 0: it has no :results entry, independent.clj:222-232) have
+ * n_words == 0. The four bitmaps (any may be NULL) receive the first
+ * min(total_words, words_cap) words; the records and the result are complete
+ * whatever the cap is. key == NULL or n_keys == 0 is one un-keyed history judged
+ * as key 0: its record and bits equal jh_check_set_bitmaps' on the same columns.
+ *
+ * Two tiers. A key whose elements span at most JH_SI_LDS_SPAN is judged by one
+ * workgroup that keeps its three bitmaps in LDS and writes each output word
+ * once; any other key marks concatenated bitmaps in device memory. The three
+ * working and four output bitmaps take 28 bytes per word: at most
+ * 28 * JH_SI_WORDS_MAX = 7 GiB.
+ *
+ * JH_EUNSUPPORTED (the shim falls back to one jh_check_set_bitmaps per key): in
+ * a keyed history an :invoke / :ok :add row or an :ok :read row without a key
+ * (it would belong to every key); an :add element of JH_NIL; a key whose span
+ * exceeds 2^34; total_words above JH_SI_WORDS_MAX; 2^31 rows or more.
+ * JH_EINVAL: a key >= n_keys; a final read's range that leaves [0, n_aux) or
+ * has a negative count; path 1 forced with a key wider than JH_SI_LDS_SPAN. */
+#define JH_SI_LDS_SPAN  (1 << 17)        /* elements per key of the on-chip tier: three 16 KiB bitmaps in LDS */
+#define JH_SI_WORDS_MAX (1LL << 28)      /* bitmap words over all keys: 7 GiB of device bitmaps, 4 GiB of output */
+
+typedef struct jh_set_indep_opts {
+    int32_t path;         /* 0 auto, 1 on-chip tier, 2 global tier; tests force both */
+    int32_t pad;
+    int64_t reserved[4];
+} jh_set_indep_opts;
+
+typedef struct jh_set_key {        /* one per key */
+    int32_t valid, cause;          /* JH_VALID / JH_INVALID / JH_UNKNOWN (JH_CAUSE_NIL_VALUE) */
+    int64_t rows;                  /* rows carrying this key; 0: the key is in no row, the shim gives it no result */
+    int64_t attempt_count, acknowledged_count, ok_count, lost_count, recovered_count, unexpected_count;
+    int64_t first_fail_entry, final_read_entry;   /* history rows, -1: none */
+    int64_t base, word_off, n_words;              /* bit i of word word_off + w of a set is element base + 32 w + i */
+} jh_set_key;
+
+typedef struct jh_set_indep_result {
+    int32_t valid, cause;          /* merge-valid over the keys that have rows */
+    int32_t path, pad;             /* 1: every key on chip, 2: some key in the global tier, 0: no key judged */
+    int64_t keys_valid, keys_invalid, keys_unknown;
+    int64_t first_fail_entry;      /* min over keys, -1 */
+    int64_t total_words;           /* sum of n_words: always the full count */
+    int64_t entries;               /* rows + final-read elements consumed */
+    double device_ms;
+} jh_set_indep_result;
+
+int jh_check_set_independent(jh_ctx *ctx, const jh_history *h, const jh_set_indep_opts *opts, jh_set_indep_result *res,
+                             jh_set_key *keys_out, uint32_t *ok, uint32_t *lost, uint32_t *unexpected,
+                             uint32_t *recovered, int64_t words_cap, char *err, size_t errlen);
 
 /* (jepsen.tests.cycle/checker (cycle/combine ...)), tests/cycle.clj:202-216,
  * 911-934, and cycle/tarjan, cycle.clj:150-160 (additive to ABI 8: new structs,

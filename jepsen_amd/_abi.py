@@ -258,6 +258,30 @@ class JhCausalReverseResult(C.Structure):
                 ("device_ms", C.c_double)]
 
 
+# (independent/checker (checker/set)), jh_check_set_independent (additive to ABI 8)
+SI_PATH_AUTO, SI_PATH_LDS, SI_PATH_GLOBAL = 0, 1, 2
+SI_LDS_SPAN = 1 << 17         # JH_SI_LDS_SPAN: elements per key of the on-chip tier
+SI_WORDS_MAX = 1 << 28        # JH_SI_WORDS_MAX: bitmap words over all keys
+SI_SPAN_MAX = 1 << 34         # elements a key may span
+SET_KEY_FIELDS = ("rows", "attempt_count", "acknowledged_count", "ok_count", "lost_count", "recovered_count",
+                  "unexpected_count", "first_fail_entry", "final_read_entry", "base", "word_off", "n_words")
+
+
+class JhSetIndepOpts(C.Structure):
+    _fields_ = [("path", C.c_int32), ("pad", C.c_int32), ("reserved", C.c_int64 * 4)]
+
+
+class JhSetKey(C.Structure):
+    _fields_ = [("valid", C.c_int32), ("cause", C.c_int32)] + [(f, C.c_int64) for f in SET_KEY_FIELDS]
+
+
+class JhSetIndepResult(C.Structure):
+    _fields_ = [("valid", C.c_int32), ("cause", C.c_int32), ("path", C.c_int32), ("pad", C.c_int32),
+                ("keys_valid", C.c_int64), ("keys_invalid", C.c_int64), ("keys_unknown", C.c_int64),
+                ("first_fail_entry", C.c_int64), ("total_words", C.c_int64), ("entries", C.c_int64),
+                ("device_ms", C.c_double)]
+
+
 CY_PROCESS, CY_REALTIME, CY_WR = 1, 2, 4
 CY_PATH_AUTO, CY_PATH_LDS, CY_PATH_GLOBAL = 0, 1, 2
 CY_LDS_VERTICES = 2048        # JH_CY_LDS_VERTICES: vertices of a region of the on-chip tier
@@ -353,9 +377,12 @@ try:
     # ... and as jh_causal_key
     CAUSAL_KEY_DTYPE = _np.dtype([("valid", _np.int32), ("kind", _np.int32), ("row", _np.int64),
                                   ("counter", _np.int64), ("last_pos", _np.int64)])
+    # ... and as jh_set_key
+    SET_KEY_DTYPE = _np.dtype([("valid", _np.int32), ("cause", _np.int32)] + [(f, _np.int64) for f in SET_KEY_FIELDS])
 except Exception:  # pragma: no cover
     VERDICT_DTYPE = None
     CAUSAL_KEY_DTYPE = None
+    SET_KEY_DTYPE = None
 
 
 def ptr64(a):

@@ -78,6 +78,9 @@ def lib():
             L.jh_check_causal_reverse.argtypes = [C.c_void_p, H, C.POINTER(A.JhCausalReverseOpts),
                                                   C.POINTER(A.JhCausalReverseResult), C.POINTER(C.c_int32), p64,
                                                   C.c_int64, p64, C.c_int64, C.c_char_p, C.c_size_t]
+            L.jh_check_set_independent.argtypes = [C.c_void_p, H, C.POINTER(A.JhSetIndepOpts),
+                                                   C.POINTER(A.JhSetIndepResult), C.POINTER(A.JhSetKey),
+                                                   p32, p32, p32, p32, C.c_int64, C.c_char_p, C.c_size_t]
             L.jh_check_causal.argtypes = [C.c_void_p, H, C.POINTER(A.JhCausalOpts), C.POINTER(A.JhCausalResult),
                                           C.POINTER(A.JhCausalKey), C.c_char_p, C.c_size_t]
             L.jh_check_g2.argtypes = [C.c_void_p, H, C.POINTER(A.JhG2Opts), C.POINTER(A.JhG2Result), p64, C.c_int64,
@@ -123,6 +126,7 @@ EXPORTED_SYMBOLS = ["jh_version", "jh_open", "jh_open_multi", "jh_open_devices",
                     "jh_check_cas", "jh_check_cas_independent_device", "jh_lin_configs", "jh_check_counter",
                     "jh_check_set", "jh_check_set_bitmaps", "jh_check_set_full", "jh_check_set_full_opts", "jh_check_total_queue", "jh_check_queue",
                     "jh_check_unique_ids", "jh_check_bank", "jh_check_long_fork", "jh_check_causal_reverse",
+                    "jh_check_set_independent",
                     "jh_check_causal", "jh_check_g2", "jh_perf",
                     "jh_scc", "jh_check_cycle",
                     "jh_host_alloc", "jh_host_free",
@@ -541,6 +545,36 @@ class Context:
         out["missing"] = miss[:min(r.missing_total, mcap)] if mcap else np.zeros(0, np.int64)
         return out
 
+    # -- independent set ------------------------------------------------------
+    def check_set_independent(self, cols, path=0, words_cap=None, on_device=False):
+        """jh_check_set_independent: the result fields plus `keys`, a structured
+        array (A.SET_KEY_DTYPE) of max(n_keys, 1) records, and `bits`, the four
+        result bitmaps (ok, lost, unexpected, recovered) of min(total_words,
+        words_cap) words: key k's sets are words [word_off, word_off + n_words)
+        over [base, base + 32 n_words). words_cap=None bounds total_words from
+        the columns on the host, so the device pass runs once."""
+        h = A.make_history(cols, on_device=on_device)
+        cap = 0 if words_cap is None else max(int(words_cap), 0)
+        if words_cap is None:
+            cap = _set_indep_words(cols) if not on_device else 1 << 16
+        keys = np.zeros(max(int(cols.n_keys), 1), A.SET_KEY_DTYPE)
+        r, o = A.JhSetIndepResult(), A.JhSetIndepOpts(path=int(path))
+        err = C.create_string_buffer(1024)
+        p32 = C.POINTER(C.c_uint32)
+        for _ in range(2):
+            bits = [np.zeros(max(cap, 1), np.uint32) for _ in range(4)]
+            rc = lib().jh_check_set_independent(self._h, C.byref(h), C.byref(o), C.byref(r),
+                                                keys.ctypes.data_as(C.POINTER(A.JhSetKey)),
+                                                *[b.ctypes.data_as(p32) for b in bits], cap, err, len(err))
+            _raise(rc, err)
+            if r.total_words <= cap or words_cap is not None:
+                break
+            cap = int(r.total_words)
+        out = {name: getattr(r, name) for name, _ in A.JhSetIndepResult._fields_ if name != "pad"}
+        out["keys"] = keys
+        out["bits"] = [b[:min(r.total_words, cap)] for b in bits]
+        return out
+
     # -- causal ---------------------------------------------------------------
     def check_causal(self, cols, on_device=False, keys=True):
         """jh_check_causal: the result fields plus `keys`, a structured array
@@ -692,6 +726,37 @@ def _set_span_words(cols):
     hi = max([int(x.max()) for x in (vals, aux) if len(x)], default=0)
     # (a span over 2^34 elements is refused by the library before any copy)
     return max(1, min(((hi - lo) >> 5) + 2, (1 << 29) + 1))
+
+
+def _set_indep_words(cols):
+    """An upper bound of jh_check_set_independent's total_words from the
+    columns: per key the span of its :add elements and of every read element of
+    its :ok :read rows (a superset of its final read's), in words."""
+    v, t, f = np.asarray(cols.value), np.asarray(cols.type), np.asarray(cols.f)
+    n_keys = int(cols.n_keys)
+    key = np.asarray(cols.key) if n_keys > 0 and cols.key is not None else np.zeros(len(v), np.int64)
+    K = max(n_keys, 1)
+    aux = np.asarray(cols.aux) if cols.aux is not None else np.zeros(0, np.int64)
+    ok = (key >= 0) & (key < K)
+    add = ok & (f == A.F_ADD) & ((t == A.TYPE_INVOKE) | (t == A.TYPE_OK)) & (v != A.NIL)
+    lo = np.full(K, np.iinfo(np.int64).max, np.int64)
+    hi = np.full(K, np.iinfo(np.int64).min, np.int64)
+    np.minimum.at(lo, key[add], v[add])
+    np.maximum.at(hi, key[add], v[add])
+    c = np.asarray(cols.value2)
+    rd = ok & (f == A.F_READ) & (t == A.TYPE_OK) & (v != A.NIL) & (v >= 0) & (c > 0) & (v <= len(aux)) & (c <= len(aux) - v)
+    rows = np.nonzero(rd)[0]
+    if len(rows):
+        # per read the min / max of its aux range (ranges may overlap or come in any order)
+        starts, counts = v[rows], c[rows]
+        idx = np.repeat(starts - np.concatenate(([0], np.cumsum(counts)[:-1])), counts) + np.arange(int(counts.sum()))
+        kk = np.repeat(key[rows], counts)
+        np.minimum.at(lo, kk, aux[idx])
+        np.maximum.at(hi, kk, aux[idx])
+    some = lo <= hi
+    d = np.where(some, hi.astype(np.uint64) - lo.astype(np.uint64), np.uint64(0))     # (exact: the difference wraps)
+    words = np.where(d < np.uint64(A.SI_SPAN_MAX), d // np.uint64(32) + np.uint64(1), np.uint64(0))   # (a wider key is refused)
+    return int(max(1, min(int(words.sum()), A.SI_WORDS_MAX + 1)))
 
 
 def bits_to_runs(words, base):

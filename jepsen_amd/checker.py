@@ -415,25 +415,63 @@ def counter():
     return Counter()
 
 
+SET_NAMES = ("ok", "lost", "unexpected", "recovered")
+
+
+def set_result(rec, bits, base):
+    """The (checker/set) result map (checker.clj:205-233) from a counts record
+    (the fields of jh_set_result / jh_set_key, a mapping or a numpy record) and
+    the four result bitmaps (ok, lost, unexpected, recovered) over [base, ...).
+    jh_check_set_bitmaps' one history and each key of jh_check_set_independent
+    go through here."""
+    from ._native import bits_to_runs
+    if int(rec["valid"]) == A.UNKNOWN:
+        return {"valid?": UNKNOWN, "error": "Set was never read"}
+    out = {"valid?": bool(int(rec["valid"]) == A.VALID),
+           "attempt-count": int(rec["attempt_count"]),
+           "acknowledged-count": int(rec["acknowledged_count"]),
+           "ok-count": int(rec["ok_count"]),
+           "lost-count": int(rec["lost_count"]),
+           "recovered-count": int(rec["recovered_count"]),
+           "unexpected-count": int(rec["unexpected_count"])}
+    for i, nm in enumerate(SET_NAMES):
+        out[nm] = _runs_str(bits_to_runs(bits[i], int(base)).tolist())
+    return out
+
+
 class SetChecker(Checker):
     """checker.clj:182-233."""
 
     def check(self, test, history, opts):
-        from ._native import bits_to_runs
         cols = _cols(history, keyed=False)
         r = _ctx().check_set_bitmaps(cols)
-        if r["valid"] == A.UNKNOWN:
-            return {"valid?": UNKNOWN, "error": "Set was never read"}
-        names = ["ok", "lost", "unexpected", "recovered"]
-        out = {"valid?": bool(r["valid"] == A.VALID),
-               "attempt-count": int(r["attempt_count"]),
-               "acknowledged-count": int(r["acknowledged_count"]),
-               "ok-count": int(r["ok_count"]),
-               "lost-count": int(r["lost_count"]),
-               "recovered-count": int(r["recovered_count"]),
-               "unexpected-count": int(r["unexpected_count"])}
-        for i, nm in enumerate(names):
-            out[nm] = _runs_str(bits_to_runs(r["bits"][i], r["base"]).tolist())
+        return set_result(r, r["bits"], r["base"])
+
+    @staticmethod
+    def check_independent(history):
+        """{key: result map} for every key of an independent history with one
+        jh_check_set_independent call, or None when the device does not judge
+        it in one call (the caller then checks key by key)."""
+        from . import _native
+        try:
+            cols = H.encode(history, keyed=True)
+        except (TypeError, ValueError, OverflowError):
+            return None
+        if not cols.ints_only or not cols.n_keys:
+            return None
+        try:
+            r = _ctx().check_set_independent(cols)
+        except _native.JhError:
+            # JH_EUNSUPPORTED, and any other refusal of the batched call: key by key, where
+            # check_safe turns what a key raises into :unknown
+            return None
+        out = {}
+        for kid, key in enumerate(cols.keys):
+            rec = r["keys"][kid]
+            if int(rec["rows"]) == 0:        # a key in no tuple: no :results entry
+                continue
+            w0, nw = int(rec["word_off"]), int(rec["n_words"])
+            out[key] = set_result(rec, [b[w0:w0 + nw] for b in r["bits"]], rec["base"])
         return out
 
 

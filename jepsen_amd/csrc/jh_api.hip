@@ -431,6 +431,25 @@ int jh_check_set_bitmaps(jh_ctx *ctx, const jh_history *h, jh_set_result *res, u
     });
 }
 
+int jh_check_set_independent(jh_ctx *ctx, const jh_history *h, const jh_set_indep_opts *opts, jh_set_indep_result *res,
+                             jh_set_key *keys_out, uint32_t *ok, uint32_t *lost, uint32_t *unexpected,
+                             uint32_t *recovered, int64_t words_cap, char *err, size_t errlen) {
+    if (!ctx || !res || !opts) { set_err(err, errlen, "null argument"); return JH_EINVAL; }
+    if (opts->path < 0 || opts->path > 2) { set_err(err, errlen, "path is 0, 1 or 2"); return JH_EINVAL; }
+    ctx = primary(ctx);
+    std::lock_guard<std::mutex> g(ctx->mu);
+    return guarded(err, errlen, [&] {
+        check_hist(h);
+        if (h->n_aux < 0) throw_jh(JH_EINVAL, "set-independent: n_aux < 0");
+        HIP_TRY(hipSetDevice(ctx->device));
+        const bool keyed = h->key != nullptr && h->n_keys > 0;
+        jh_history d = stage_history(ctx, h, keyed, true);
+        if (!keyed) d.key = nullptr;
+        uint32_t *bits[4] = {ok, lost, unexpected, recovered};
+        set_independent_check(ctx, &d, opts, res, keys_out, bits, words_cap, ctx->stream);
+    });
+}
+
 int jh_host_alloc(size_t bytes, void **out, char *err, size_t errlen) {
     if (!out) { set_err(err, errlen, "null argument"); return JH_EINVAL; }
     *out = nullptr;

@@ -140,6 +140,7 @@ enum WsSlot {
     WS_G2_META, WS_G2_CNT, WS_G2_WORDS, WS_G2_TCNT, WS_G2_TBASE, WS_G2_TMP, WS_G2_MIN, WS_G2_OUT,
     WS_PF_META, WS_PF_TIME, WS_PF_TMP, WS_PF_K64A, WS_PF_K64B, WS_PF_K64C, WS_PF_K64D, WS_PF_V32A, WS_PF_V32B,
     WS_PF_K32A, WS_PF_K32B, WS_PF_PAIR, WS_PF_RUN_U, WS_PF_RUN_C, WS_PF_RUN_S, WS_PF_NRUNS, WS_PF_OUT,
+    WS_SI_KEYS, WS_SI_META, WS_SI_WORDS, WS_SI_TMP, WS_SI_BITS, WS_SI_OUT, WS_SI_RECS,
     WS_COUNT
 };
 
@@ -212,6 +213,9 @@ void set_check(jh_ctx *ctx, const jh_history *dh, jh_set_result *res, int64_t *r
                int64_t runs_cap, hipStream_t stream);
 void set_check_bitmaps(jh_ctx *ctx, const jh_history *dh, jh_set_result *res, uint32_t *bits_out[4],
                        int64_t words_cap, int64_t *base, int64_t *n_words, hipStream_t stream);
+// independent set (jh_setindep.hip); keys_out = max(n_keys, 1) host records (or null), bits_out = {ok, lost, unexpected, recovered}
+void set_independent_check(jh_ctx *ctx, const jh_history *dh, const jh_set_indep_opts *opts, jh_set_indep_result *res,
+                           jh_set_key *keys_out, uint32_t *bits_out[4], int64_t words_cap, hipStream_t stream);
 // set-full (jh_setfull.hip); lists_out = {lost, never-read, stale}
 void set_full_check(jh_ctx *ctx, const jh_history *dh, const int64_t *time_dev, bool linearizable, int64_t read_batch,
                     jh_set_full_result *res, int64_t *lists_out[3], int64_t list_cap, hipStream_t stream);

@@ -8409,3 +8409,18 @@ void key_index(jh_ctx *ctx, const jh_history *dh, int64_t *key_off, int64_t *row
     }
 }
 
+// The same partition left on the device (jh_setindep.hip walks each key's rows
+// through it): rows sorted by key, K + 1 segment offsets, the un-keyed rows last.
+void key_partition_device(jh_ctx *ctx, const jh_history *dh, const uint32_t **rows, const uint32_t **off,
+                          hipStream_t st) {
+    const int64_t n = dh->n, K = dh->n_keys;
+    if (K >= (1LL << 31) - 2) throw_jh(JH_EUNSUPPORTED, "more than 2^31 keys");
+    if (n >= (1LL << 31)) throw_jh(JH_EUNSUPPORTED, "more than 2^31 entries");
+    KeyPartition kp = partition_buffers(ctx, n);
+    kp.off = ctx->ws<uint32_t>(WS_SEG_OFF, K + 2);
+    RangeOut *ro = ctx->ws<RangeOut>(WS_MISC, 1);
+    partition_by_key(ctx, kp, dh->key, n, K, true, ro, st);
+    *rows = kp.rB;
+    *off = kp.off;
+}
+

@@ -12,7 +12,7 @@
 // Elements live in [vmin, vmax]; each of the three sets is a bitmap over that
 // span (atomicOr of 32-bit words), every set operation is a word-wise
 // boolean, and runs fall out of the bit boundaries of each word.
-#include "jh_prims.h"
+#include "jh_set_bits.h"
 
 namespace {
 
@@ -139,48 +139,6 @@ __global__ void __launch_bounds__(256) k_set_range(const int64_t *__restrict__ a
         if (lo != LLONG_MAX) atomicMin(&m->vmin, lo);
         if (hi != LLONG_MIN) atomicMax(&m->vmax, hi);
     }
-}
-
-// Marking: each workgroup takes a contiguous chunk of MARK_CH rows (or read
-// elements) and merges its bits in LDS before touching HBM.
-//  * Within a wave, lanes holding the same bitmap word are merged by a
-//    segmented OR scan over lanes (shuffles); only the last lane of each run
-//    writes. Jepsen's set elements are mostly written and read in ascending
-//    order, so a wave's 64 elements fall into two or three words.
-//  * Those few writes go to a direct-mapped LDS cache of words (tag + bits);
-//    a word whose slot holds another word goes straight to HBM.
-//  * At the end the cache is flushed: one global atomicOr per cached word.
-// Any element order stays correct (unmerged lanes just write on their own).
-constexpr int MARK_CH = 16384, MARK_SLOTS = 2048;
-constexpr long long MARK_EMPTY = -1;
-
-__device__ __forceinline__ void mark_bits(uint32_t *bm, long long *tag, uint32_t *lb, long long w, uint32_t bits) {
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const long long wn = __shfl_up(w, o);
-        const uint32_t bn = (uint32_t)__shfl_up((int)bits, o);
-        if (lane >= o && wn == w) bits |= bn;
-    }
-    const long long wnext = __shfl_down(w, 1);
-    const bool tail = lane == 63 || wnext != w;
-    if (w < 0 || !tail) return;
-    const int sl = (int)(w & (MARK_SLOTS - 1));
-    long long t = tag[sl];
-    if (t == MARK_EMPTY)
-        t = (long long)atomicCAS((unsigned long long *)&tag[sl], (unsigned long long)MARK_EMPTY, (unsigned long long)w);
-    if (t == MARK_EMPTY || t == w) atomicOr(&lb[sl], bits);
-    else atomicOr(&bm[w], bits);
-}
-
-__device__ __forceinline__ void mark_init(long long *tag, uint32_t *lb) {
-    for (int i = threadIdx.x; i < MARK_SLOTS; i += blockDim.x) { tag[i] = MARK_EMPTY; lb[i] = 0; }
-    __syncthreads();
-}
-__device__ __forceinline__ void mark_flush(uint32_t *bm, const long long *tag, const uint32_t *lb) {
-    __syncthreads();
-    for (int i = threadIdx.x; i < MARK_SLOTS; i += blockDim.x)
-        if (tag[i] != MARK_EMPTY && lb[i]) atomicOr(&bm[tag[i]], lb[i]);
 }
 
 // one pass over the rows (24 B each): :invoke :add elements into A, :ok :add
@@ -484,16 +442,6 @@ __global__ void __launch_bounds__(256) k_set_pack_bits(const uint8_t *__restrict
         }
         bits[w] = out;
     }
-}
-
-__device__ __forceinline__ void set_words(const uint32_t *A, const uint32_t *D, const uint32_t *R,
-                                          int64_t w, int64_t nw, uint32_t out[4]) {
-    const uint32_t a = A[w], d = D[w], r = R[w];
-    const uint32_t ok = r & a;
-    out[0] = ok;          // ok
-    out[1] = d & ~r;      // lost
-    out[2] = r & ~a;      // unexpected
-    out[3] = ok & ~d;     // recovered
 }
 
 // per word: population counts and run-start counts of the four result sets;

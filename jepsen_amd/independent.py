@@ -6,12 +6,13 @@ once and ALL keys are checked by one libjh call (splitter + per-key WGL on
 the GPU); any other composed checkers still run per key on their own. When it
 is (or composes) a causal-reverse checker, every key's reads are judged by one
 jh_check_causal_reverse call in the same way, and a causal checker over
-(causal-register) judges every key with one jh_check_causal call.
+(causal-register) judges every key with one jh_check_causal call, and a
+(checker/set) judges every key with one jh_check_set_independent call.
 """
 from . import _abi as A
 from . import history as H
-from .checker import (Checker, Compose, Linearizable, _algorithm, add_configs, check_safe, lin_result, merge_valid,
-                      wants_configs, _init_state, _ctx)
+from .checker import (Checker, Compose, Linearizable, SetChecker, _algorithm, add_configs, check_safe, lin_result,
+                      merge_valid, wants_configs, _init_state, _ctx)
 from .causal_reverse import CausalReverseChecker, check_independent as _cr_check_independent
 from .causal import CausalChecker, check_independent as _cm_check_independent
 from .model import to_device_ops
@@ -122,6 +123,26 @@ def _cm_member(inner):
     return None, None
 
 
+def _set_member(inner):
+    if isinstance(inner, SetChecker):
+        return None, inner
+    if isinstance(inner, Compose):
+        for name, c in inner.checker_map.items():
+            if isinstance(c, SetChecker):
+                return name, c
+    return None, None
+
+
+def check_per_key(inner, test, history):
+    """{key: result} of the generic path: every key's subhistory through the
+    inner checker (per-key device calls)."""
+    results = {}
+    for key, sub in subhistories(history).items():
+        results[key] = check_safe(inner, test, sub,
+                                  {"subdirectory": [DIR, key], "history-key": key})
+    return results
+
+
 class IndependentChecker(Checker):
     """independent.clj:247-298."""
 
@@ -218,13 +239,24 @@ class IndependentChecker(Checker):
                 r["valid?"] = merge_valid(x.get("valid?") if isinstance(x, dict) else None for x in r.values())
                 results[key] = r
             return self._results_map(results)
+        st_name, st = _set_member(self.inner) if lin is None and cr is None and cm is None else (None, None)
+        st_res = st.check_independent(history) if st is not None else None
+        if st_res is not None:
+            if st_name is None:
+                return self._results_map(st_res)
+            results = {}
+            subs = subhistories(history, list(st_res))
+            for key, res in st_res.items():
+                r = {}
+                for nm, c in self.inner.checker_map.items():
+                    r[nm] = res if nm == st_name else check_safe(
+                        c, test, subs[key], {"subdirectory": [DIR, key], "history-key": key})
+                r["valid?"] = merge_valid(x.get("valid?") if isinstance(x, dict) else None for x in r.values())
+                results[key] = r
+            return self._results_map(results)
         # generic path: every key through the inner checker (per-key device
         # calls for a linearizable inner)
-        results = {}
-        for key, sub in subhistories(history).items():
-            results[key] = check_safe(self.inner, test, sub,
-                                      {"subdirectory": [DIR, key], "history-key": key})
-        return self._results_map(results)
+        return self._results_map(check_per_key(self.inner, test, history))
 
 
 def checker(inner):

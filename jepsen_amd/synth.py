@@ -1178,6 +1178,111 @@ def g2_columns_to_ops(cols):
     return out
 
 
+# ---------------------------------------------------------------------------
+# independent set workload, aerospike/src/aerospike/set.clj:48-72
+def independent_set_history(n_keys=64, adds_per_key=100, threads_per_key=5, p_fail=0.05, p_info=0.02, n_lost_keys=0,
+                            n_unexpected_keys=0, seed=0, concurrent=4, p_vector=0.25, nemesis_every=500):
+    """A keyed set history as Columns (standard encoding: set reads in aux), the
+    independent/concurrent-generator shape of aerospike's set workload: keys run
+    in groups of `concurrent`, each on threads_per_key threads; a key is
+    adds_per_key :add ops of the elements 0, 1, ... in ascending order (an
+    invocation and an :ok / :fail / :info completion each), and after every add
+    of every key one final :read per key (invocation and :ok). A read holds the
+    key's acknowledged elements and each :info element with probability 1/2;
+    n_lost_keys keys miss up to three acknowledged elements and
+    n_unexpected_keys keys read up to three elements nobody added. Reads are
+    ascending, except that with p_vector a read's elements are shuffled (a vector
+    :value). Un-keyed :nemesis :info rows come every nemesis_every rows or so."""
+    from . import _abi as A
+    rng = np.random.default_rng(seed)
+    K, N, T, G = int(n_keys), int(adds_per_key), max(int(threads_per_key), 1), max(int(concurrent), 1)
+    u = rng.random((K, N))
+    ctype = np.where(u < p_fail, A.TYPE_FAIL, np.where(u < p_fail + p_info, A.TYPE_INFO, A.TYPE_OK))
+    # the final reads: N + 3 candidate elements per key
+    present = np.zeros((K, N + 3), bool)
+    present[:, :N] = (ctype == A.TYPE_OK) | ((ctype == A.TYPE_INFO) & (rng.random((K, N)) < 0.5))
+    picks = rng.permutation(K)
+    lost_keys, unexp_keys = picks[:min(int(n_lost_keys), K)], picks[::-1][:min(int(n_unexpected_keys), K)]
+    if N > 0:
+        for k in lost_keys:
+            acked = np.nonzero(ctype[k] == A.TYPE_OK)[0]
+            present[k, rng.choice(acked, size=min(3, len(acked)), replace=False)] = False
+    for j, k in enumerate(unexp_keys):
+        present[k, N:N + 1 + j % 3] = True
+    rk, re = np.nonzero(present)
+    cnt = present.sum(axis=1)
+    shuf = rng.random(K) < p_vector
+    order = np.lexsort((np.where(shuf[rk], rng.random(len(rk)) * (N + 3), re), rk))
+    aux = re[order].astype(np.int64)
+    roff = np.concatenate(([0], np.cumsum(cnt)[:-1])).astype(np.int64)
+    # times: a key's group starts when the one before it is done; the reads come after every add
+    g0 = (np.arange(K) // G * (N + T + 2.0))[:, None]
+    t_inv = g0 + np.arange(N)[None, :] + 0.5 * rng.random((K, N))
+    t_cmp = t_inv + 0.05 + 0.9 * T * rng.random((K, N))
+    t_end = float(t_cmp.max()) + 1.0 if N and K else 1.0
+    t_rinv = t_end + (np.arange(K) // G * 4.0) + rng.random(K)
+    t_rcmp = t_rinv + 0.05 + rng.random(K)
+    n_client = 2 * K * N + 2 * K
+    n_nem = n_client // max(int(nemesis_every), 1) if nemesis_every else 0
+    t_nem = rng.random(n_nem) * (float(t_rcmp.max()) if K else 1.0)
+    times = np.concatenate([t_inv.ravel(), t_cmp.ravel(), t_rinv, t_rcmp, t_nem])
+    n = len(times)
+    row_of = np.empty(n, np.int64)
+    row_of[np.argsort(times, kind="stable")] = np.arange(n)
+    kk = np.repeat(np.arange(K), N)
+    ee = np.tile(np.arange(N), K)
+    proc_add = (kk % G) * T + ee % T
+    proc = np.full(n, -1, np.int64)
+    typ = np.full(n, A.TYPE_INFO, np.int64)
+    f = np.full(n, A.F_FIRST_INTERNED, np.int64)
+    key = np.full(n, -1, np.int64)
+    val = np.full(n, A.NIL, np.int64)
+    val2 = np.full(n, A.NIL, np.int64)
+    a, b = K * N, 2 * K * N
+    for rows, ty in ((row_of[:a], A.TYPE_INVOKE), (row_of[a:b], ctype.ravel())):
+        proc[rows] = proc_add; typ[rows] = ty; f[rows] = A.F_ADD; key[rows] = kk; val[rows] = ee
+    ri, rc = row_of[b:b + K], row_of[b + K:b + 2 * K]
+    for rows in (ri, rc):
+        proc[rows] = (np.arange(K) % G) * T; f[rows] = A.F_READ; key[rows] = np.arange(K)
+    typ[ri] = A.TYPE_INVOKE
+    typ[rc] = A.TYPE_OK
+    val[rc] = roff
+    val2[rc] = cnt
+    # key ids in first-appearance order, as the encoder interns them
+    first = np.full(K, n, np.int64)
+    np.minimum.at(first, key[key >= 0], np.nonzero(key >= 0)[0])
+    by_first = np.argsort(first, kind="stable")
+    new_id = np.empty(K, np.int64)
+    new_id[by_first] = np.arange(K)
+    key[key >= 0] = new_id[key[key >= 0]]
+    return Columns(n=n, process=proc, type=typ, f=f, key=key, value=val, value2=val2, n_keys=K,
+                   aux=aux if len(aux) else np.zeros(1, np.int64), keys=by_first.tolist(), f_names=["start"])
+
+
+def independent_set_columns_to_ops(cols):
+    """Op maps of an independent set history's Columns: independent tuples for
+    keyed rows, a read's :value the list of its elements in aux order."""
+    from . import _abi as A
+    from .history import TYPE_NAMES, tuple_
+    out = []
+    for i in range(cols.n):
+        p, fi, k = int(cols.process[i]), int(cols.f[i]), int(cols.key[i])
+        op = {"process": p if p >= 0 else "nemesis", "type": TYPE_NAMES[int(cols.type[i])]}
+        v = None if int(cols.value[i]) == A.NIL else int(cols.value[i])
+        if fi == A.F_ADD:
+            op["f"] = "add"
+        elif fi == A.F_READ:
+            op["f"] = "read"
+            if v is not None and int(cols.type[i]) == A.TYPE_OK:
+                v = [int(x) for x in cols.aux[v:v + int(cols.value2[i])]]
+        else:
+            j = fi - A.F_FIRST_INTERNED
+            op["f"] = cols.f_names[j] if 0 <= j < len(cols.f_names) else "start"
+        op["value"] = tuple_(cols.keys[k], v) if k >= 0 else v
+        out.append(op)
+    return out
+
+
 def perf_history(n=4096, procs=5, fs=("read", "write", "cas"), seed=0, p_fail=0.1, p_info=0.05, nemesis_every=1000,
                  dangling=False, mean_latency_ms=20.0, mean_think_ms=5.0):
     """A history for checker/perf as Columns with a `time` attribute (integer
