@@ -41,6 +41,8 @@
  *                                 the reduction behind the three plots
  *                                                   jepsen/src/jepsen/checker.clj:736-768
  *                                                   jepsen/src/jepsen/checker/perf.clj
+ *   jh_check_multi_register   <- (independent/checker (checker/linearizable {:model (multi-register {})}))
+ *                                                   yugabyte/src/yugabyte/multi_key_acid.clj:20-42,112-127
  *
  * Plain pointers and sizes only. The caller owns every buffer; the library
  * never retains a caller pointer after returning. All entry points are
@@ -1322,6 +1324,67 @@ typedef struct jh_perf_result {
 int jh_perf(jh_ctx *ctx, const jh_history *h, const int64_t *time, const jh_perf_opts *opts, jh_perf_result *res,
             int64_t *pair, int64_t pair_cap, int64_t *pt_row, int64_t pt_cap, int64_t *series, int64_t series_cap,
             int64_t *groups, int64_t group_cap, int64_t *cells, int64_t cell_cap, char *err, size_t errlen);
+
+/* (independent/checker (checker/linearizable {:model (multi-register init)})),
+ * yugabyte/src/yugabyte/multi_key_acid.clj:20-42,112-127 (additive to ABI 8).
+ * The model's state is a map register -> value; an op is a txn [[f k v] ...] of
+ * reads and writes applied left to right; a read of nil is always legal.
+ *
+ * Multi-register txns (this entry point only): EVERY client row (:invoke, :ok,
+ * :fail, :info) carries its txn in the "Cycle txns" layout: value = the index
+ * of its first micro-op, value2 = its number of micro-ops, micro-op j the triple
+ * aux[3*(value+j) .. +3) = [f, reg, val] with f = JH_F_READ / JH_F_WRITE; a nil
+ * :value is value = JH_NIL (value2 not read). The caller interns registers to
+ * 0 .. n_regs-1 (registers that stand only in the initial map count) and values
+ * to dense ids 1 .. V; nil is JH_NIL or id 0. The state is one 32-bit word,
+ * `bits` = ceil(log2(V + 1)) bits per register, register r at bit r * bits.
+ * `key` as in jh_check_cas_independent; key == NULL or n_keys == 0 is one
+ * un-keyed history (out has one entry).
+ *
+ * A txn reduces, whatever the state, to (never, rmask, rval, wmask, wval):
+ *   step(s) = (never or (s & rmask) != rval) ? inconsistent : (s & ~wmask) | wval
+ * (a nil read adds nothing; a non-nil read of a register the txn wrote or read
+ * before is compared with that value, a mismatch sets never; a write, nil
+ * included, sets wmask / wval, a later one overwrites).
+ *
+ * Per key: invoke and completion are paired per process (an :info row never
+ * completes: the op is crashed); a double invoke / an orphan completion make
+ * the key JH_UNKNOWN with JH_CAUSE_DOUBLE_INVOKE / JH_CAUSE_ORPHAN (the
+ * smallest such row decides). An :ok op's txn is its completion's when that
+ * row's value is not JH_NIL, else its invocation's; a crashed op keeps its
+ * invocation's (PARITY-UNPINNED: knossos is not vendored). Dropped: rows of a
+ * process < 0, failed ops, crashed ops without a write, :ok ops whose normal
+ * form is the identity. The rest is searched by WGL exactly as the cas path
+ * (same order, explored = the cache size, budget as jh_lin_opts.budget):
+ *   valid / cause / fail_entry / explored as in jh_key_verdict; previous_ok =
+ *   last_op = -1; analyzer = JH_ANALYZER_WGL. A key in no client row: JH_VALID,
+ *   explored = -1. More than JH_MR_MAX_WINDOW searched ops open at an :ok
+ *   return besides the returning one, or 2^20 - 1 or more searched :ok ops:
+ *   JH_UNKNOWN / JH_CAUSE_WINDOW for that key alone, explored = 0.
+ * sum (may be NULL) receives valid, n_invalid, n_unknown, first_fail_entry,
+ * n_keys, explored, device_ms and waves[0] (the search waves launched); every
+ * other field of ABI 8's layout is 0.
+ *
+ * JH_EUNSUPPORTED (the shim falls back to its host checker): n_regs * bits > 32;
+ * a txn of more than JH_CY_MAX_MOPS micro-ops; in a keyed history a client row
+ * without a key; 2^31 rows or more. JH_EINVAL: a triple range leaving aux or a
+ * negative count; reg outside [0, n_regs); a value id outside [0, 2^bits) (and
+ * not JH_NIL), in a txn or in init; an f other than read / write on a client
+ * row that is not :fail; a key >= n_keys. */
+#define JH_MR_MAX_WINDOW 64
+#define JH_MR_GEN_JUMP   1          /* flags, test hook: every memo table is cleared and its generations start just below their wrap */
+
+typedef struct jh_multi_register_opts {
+    int64_t budget;            /* max memo inserts per key before :unknown; <= 0: JH_DEFAULT_BUDGET */
+    int32_t n_regs, bits;
+    const int64_t *init;       /* n_regs value ids (host; 0 or JH_NIL = nil); NULL: every register nil */
+    int32_t waves;             /* search waves; <= 0: min(keys, 4 per CU, what a quarter of free memory holds) */
+    int32_t flags;             /* JH_MR_*; 0 in production */
+    int64_t reserved[4];
+} jh_multi_register_opts;
+
+int jh_check_multi_register(jh_ctx *ctx, const jh_history *h, const jh_multi_register_opts *opts,
+                            jh_key_verdict *out /*[max(n_keys, 1)]*/, jh_summary *sum, char *err, size_t errlen);
 
 #ifdef __cplusplus
 }

@@ -271,6 +271,17 @@ class JhSetIndepOpts(C.Structure):
     _fields_ = [("path", C.c_int32), ("pad", C.c_int32), ("reserved", C.c_int64 * 4)]
 
 
+# (independent/checker (checker/linearizable {:model (multi-register init)})), jh_check_multi_register (additive to ABI 8)
+MR_MAX_WINDOW = 64
+MR_MAX_MOPS = 64              # JH_CY_MAX_MOPS
+MR_GEN_JUMP = 1
+
+
+class JhMultiRegisterOpts(C.Structure):
+    _fields_ = [("budget", C.c_int64), ("n_regs", C.c_int32), ("bits", C.c_int32), ("init", _p64),
+                ("waves", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int64 * 4)]
+
+
 class JhSetKey(C.Structure):
     _fields_ = [("valid", C.c_int32), ("cause", C.c_int32)] + [(f, C.c_int64) for f in SET_KEY_FIELDS]
 

@@ -81,6 +81,9 @@ def lib():
             L.jh_check_set_independent.argtypes = [C.c_void_p, H, C.POINTER(A.JhSetIndepOpts),
                                                    C.POINTER(A.JhSetIndepResult), C.POINTER(A.JhSetKey),
                                                    p32, p32, p32, p32, C.c_int64, C.c_char_p, C.c_size_t]
+            L.jh_check_multi_register.argtypes = [C.c_void_p, H, C.POINTER(A.JhMultiRegisterOpts),
+                                                  C.POINTER(A.JhKeyVerdict), C.POINTER(A.JhSummary),
+                                                  C.c_char_p, C.c_size_t]
             L.jh_check_causal.argtypes = [C.c_void_p, H, C.POINTER(A.JhCausalOpts), C.POINTER(A.JhCausalResult),
                                           C.POINTER(A.JhCausalKey), C.c_char_p, C.c_size_t]
             L.jh_check_g2.argtypes = [C.c_void_p, H, C.POINTER(A.JhG2Opts), C.POINTER(A.JhG2Result), p64, C.c_int64,
@@ -126,7 +129,7 @@ EXPORTED_SYMBOLS = ["jh_version", "jh_open", "jh_open_multi", "jh_open_devices",
                     "jh_check_cas", "jh_check_cas_independent_device", "jh_lin_configs", "jh_check_counter",
                     "jh_check_set", "jh_check_set_bitmaps", "jh_check_set_full", "jh_check_set_full_opts", "jh_check_total_queue", "jh_check_queue",
                     "jh_check_unique_ids", "jh_check_bank", "jh_check_long_fork", "jh_check_causal_reverse",
-                    "jh_check_set_independent",
+                    "jh_check_set_independent", "jh_check_multi_register",
                     "jh_check_causal", "jh_check_g2", "jh_perf",
                     "jh_scc", "jh_check_cycle",
                     "jh_host_alloc", "jh_host_free",
@@ -546,6 +549,25 @@ class Context:
         return out
 
     # -- independent set ------------------------------------------------------
+    def check_multi_register(self, cols, n_regs, bits, init=None, budget=None, waves=0, flags=0):
+        """jh_check_multi_register over columns in the multi-register txn layout
+        (jepsen_amd.multi_register.encode): (verdicts [max(n_keys, 1)] of
+        VERDICT_DTYPE, JhSummary). init: n_regs value ids, or None."""
+        h = A.make_history(cols)
+        out = np.zeros(max(cols.n_keys, 1), dtype=A.VERDICT_DTYPE)
+        s = A.JhSummary()
+        o = A.JhMultiRegisterOpts(budget=int(budget or 0), n_regs=int(n_regs), bits=int(bits), waves=int(waves),
+                                  flags=int(flags))
+        ini = None
+        if init is not None:
+            ini = np.ascontiguousarray(init, np.int64)
+            o.init = A.ptr64(ini) if len(ini) else None
+        err = C.create_string_buffer(1024)
+        rc = lib().jh_check_multi_register(self._h, C.byref(h), C.byref(o), out.ctypes.data_as(C.POINTER(A.JhKeyVerdict)),
+                                           C.byref(s), err, len(err))
+        _raise(rc, err)
+        return out, s
+
     def check_set_independent(self, cols, path=0, words_cap=None, on_device=False):
         """jh_check_set_independent: the result fields plus `keys`, a structured
         array (A.SET_KEY_DTYPE) of max(n_keys, 1) records, and `bits`, the four

@@ -17,7 +17,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
-HIP_SOURCES = ["jh_lin.hip", "jh_counter.hip", "jh_set.hip", "jh_setindep.hip", "jh_setfull.hip", "jh_queue.hip", "jh_uids.hip", "jh_bank.hip", "jh_longfork.hip", "jh_causal.hip", "jh_causalreg.hip", "jh_g2.hip", "jh_perf.hip", "jh_cycle.hip", "jh_cycle_append.hip", "jh_cycle_mono.hip", "jh_api.hip", "jh_multi.hip", "jh_ingest.hip"]
+HIP_SOURCES = ["jh_lin.hip", "jh_linmr.hip", "jh_counter.hip", "jh_set.hip", "jh_setindep.hip", "jh_setfull.hip", "jh_queue.hip", "jh_uids.hip", "jh_bank.hip", "jh_longfork.hip", "jh_causal.hip", "jh_causalreg.hip", "jh_g2.hip", "jh_perf.hip", "jh_cycle.hip", "jh_cycle_append.hip", "jh_cycle_mono.hip", "jh_api.hip", "jh_multi.hip", "jh_ingest.hip"]
 HOST_SOURCES = ["jh_io.cpp"]
 # every header directly under csrc/ (a new one cannot be forgotten), and the public one
 HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(ROOT, "include", "jh.h")]

@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _abi as A
 from . import history as H
-from .model import CASRegister, Mutex, Register, UnorderedQueue, is_inconsistent, to_device_ops
+from .model import CASRegister, MultiRegister, Mutex, Register, UnorderedQueue, is_inconsistent, to_device_ops
 
 UNKNOWN = "unknown"
 
@@ -220,7 +220,8 @@ def op_at(cols, ops, row):
 
 
 class Linearizable(Checker):
-    """checker.clj:127-158 with {:model (cas-register v)}. :algorithm :wgl and
+    """checker.clj:127-158 with {:model (cas-register v)} (a register and a mutex
+    are searched as one; a multi-register by jepsen_amd/multi_register.py). :algorithm :wgl and
     the default (competition) report the WGL analysis; :linear runs the
     JIT-linearization analysis (the reachable configuration set) on every
     key it can hold and WGL on the rest -- each key's :analyzer says which.
@@ -235,11 +236,15 @@ class Linearizable(Checker):
         self.budget = opts.get("budget")
 
     def supported(self):
-        return isinstance(self.model, (CASRegister, Register, Mutex))
+        return isinstance(self.model, (CASRegister, Register, Mutex, MultiRegister))
 
     def check(self, test, history, opts):
         if not self.supported():
             raise NotImplementedError(f"model {self.model!r} has no device implementation")
+        if isinstance(self.model, MultiRegister):
+            # a txn search of its own (jh_check_multi_register); :configs and :final-paths stay empty
+            from . import multi_register
+            return multi_register.check(history, self.model, self.budget)
         ops = None
         if not isinstance(history, H.Columns):
             ops = list(history)

@@ -450,6 +450,22 @@ int jh_check_set_independent(jh_ctx *ctx, const jh_history *h, const jh_set_inde
     });
 }
 
+int jh_check_multi_register(jh_ctx *ctx, const jh_history *h, const jh_multi_register_opts *opts, jh_key_verdict *out,
+                            jh_summary *sum, char *err, size_t errlen) {
+    if (!ctx || !opts || !out) { set_err(err, errlen, "null argument"); return JH_EINVAL; }
+    ctx = primary(ctx);
+    std::lock_guard<std::mutex> g(ctx->mu);
+    return guarded(err, errlen, [&] {
+        check_hist(h);
+        if (h->n_aux < 0 || h->n_aux % 3) throw_jh(JH_EINVAL, "multi-register: n_aux is not a multiple of 3");
+        HIP_TRY(hipSetDevice(ctx->device));
+        const bool keyed = h->key != nullptr && h->n_keys > 0;
+        jh_history d = stage_history(ctx, h, keyed, true);
+        if (!keyed) { d.key = nullptr; d.n_keys = 0; }
+        multi_register_check(ctx, &d, opts, out, sum, ctx->stream);
+    });
+}
+
 int jh_host_alloc(size_t bytes, void **out, char *err, size_t errlen) {
     if (!out) { set_err(err, errlen, "null argument"); return JH_EINVAL; }
     *out = nullptr;

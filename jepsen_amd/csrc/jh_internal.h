@@ -70,6 +70,7 @@ struct jh_ctx {
     size_t pinned_bytes = 0;
     std::vector<jh_ctx *> members;  // jh_open_multi: one context per device (jh_multi.hip); empty otherwise
     struct Ingest *ingest = nullptr;  // host-buffer staging: packing threads, pinned chunks (jh_ingest.hip)
+    size_t mr_cap = 0;              // entries per multi-register memo table whose generation tags are live (jh_linmr.hip)
 
     template <class T>
     T *ws(int slot, size_t count, bool zero = false) {
@@ -141,6 +142,10 @@ enum WsSlot {
     WS_PF_META, WS_PF_TIME, WS_PF_TMP, WS_PF_K64A, WS_PF_K64B, WS_PF_K64C, WS_PF_K64D, WS_PF_V32A, WS_PF_V32B,
     WS_PF_K32A, WS_PF_K32B, WS_PF_PAIR, WS_PF_RUN_U, WS_PF_RUN_C, WS_PF_RUN_S, WS_PF_NRUNS, WS_PF_OUT,
     WS_SI_KEYS, WS_SI_META, WS_SI_WORDS, WS_SI_TMP, WS_SI_BITS, WS_SI_OUT, WS_SI_RECS,
+    WS_MR_META, WS_MR_TMP, WS_MR_NF, WS_MR_FLAG, WS_MR_ROLE, WS_MR_LINK, WS_MR_SRC, WS_MR_SKEY, WS_MR_SKEY2, WS_MR_ROWID,
+    WS_MR_ROWS, WS_MR_OFF, WS_MR_INC, WS_MR_PK, WS_MR_PK2, WS_MR_RA, WS_MR_RB, WS_MR_KB, WS_MR_KB2, WS_MR_VIOL,
+    WS_MR_KEYS, WS_MR_CNT, WS_MR_SCAN, WS_MR_OPIDX, WS_MR_OPS, WS_MR_OPRR, WS_MR_LAYERS, WS_MR_WND, WS_MR_COST,
+    WS_MR_COST2, WS_MR_ORDER, WS_MR_ORDER2, WS_MR_MEMO, WS_MR_STACK, WS_MR_GEN, WS_MR_OUT, WS_MR_TABS,
     WS_COUNT
 };
 
@@ -242,6 +247,9 @@ void causal_check(jh_ctx *ctx, const jh_history *dh, jh_causal_result *res, jh_c
 // adya g2 (jh_g2.hip); illegal_out = [key id, count] pairs
 void g2_check(jh_ctx *ctx, const jh_history *dh, jh_g2_result *res, int64_t *illegal_out, int64_t illegal_cap,
               hipStream_t stream);
+// multi-register linearizability (jh_linmr.hip); out = max(n_keys, 1) host verdicts, sum may be null
+void multi_register_check(jh_ctx *ctx, const jh_history *dh, const jh_multi_register_opts *opts, jh_key_verdict *out,
+                          jh_summary *sum, hipStream_t stream);
 // perf (jh_perf.hip); dh's process / type / f and time_dev are device columns, the outputs host buffers (any may be null)
 struct PerfOut {
     int64_t *pair, pair_cap, *pt_row, pt_cap, *series, series_cap, *groups, group_cap, *cells, cell_cap;

@@ -15,7 +15,7 @@ from .checker import (Checker, Compose, Linearizable, SetChecker, _algorithm, ad
                       merge_valid, wants_configs, _init_state, _ctx)
 from .causal_reverse import CausalReverseChecker, check_independent as _cr_check_independent
 from .causal import CausalChecker, check_independent as _cm_check_independent
-from .model import to_device_ops
+from .model import MultiRegister, to_device_ops
 
 DIR = "independent"
 tuple_ = H.tuple_
@@ -155,9 +155,39 @@ class IndependentChecker(Checker):
                 "results": results,
                 "failures": failures}
 
+    def _check_multi_register(self, test, history, name, lin):
+        """Every key of a multi-register linearizable (or of the compose that
+        holds one, the other members per key on (subhistory k)) from one
+        jh_check_multi_register call; None where a client op carries no key."""
+        from . import multi_register
+        if any(multi_register._client(op.get("process")) and not is_tuple(op.get("value")) for op in history):
+            return None
+        try:
+            verdicts, _ = multi_register.verdicts(history, lin.model, lin.budget, keyed=True)
+        except ValueError:
+            return None                       # a micro-op without a clause: per key, where check-safe keeps it
+        unwrapped = [dict(op, value=op["value"].val) if is_tuple(op.get("value")) else op for op in history]
+        lin_res = {key: multi_register.result_map(v, unwrapped) for key, v in verdicts.items()}
+        if name is None:
+            return self._results_map(lin_res)
+        results = {}
+        subs = subhistories(history, list(lin_res))
+        for key, lr in lin_res.items():
+            r = {}
+            for nm, c in self.inner.checker_map.items():
+                r[nm] = lr if nm == name else check_safe(c, test, subs[key], {"subdirectory": [DIR, key], "history-key": key})
+            r["valid?"] = merge_valid(x.get("valid?") if isinstance(x, dict) else None for x in r.values())
+            results[key] = r
+        return self._results_map(results)
+
     def check(self, test, history, opts):
         history = list(history)
         name, lin = _lin_member(self.inner)
+        if lin is not None and isinstance(lin.model, MultiRegister):
+            mr = self._check_multi_register(test, history, name, lin)
+            if mr is not None:
+                return mr
+            return self._results_map(check_per_key(self.inner, test, history))
         if lin is not None:
             try:
                 dev_history = to_device_ops(lin.model, history)

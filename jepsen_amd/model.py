@@ -135,6 +135,71 @@ def unordered_queue():
     return UnorderedQueue()
 
 
+def pr_str(v):
+    """Clojure's pr-str of a register value: nil, strings quoted, keywords bare."""
+    if v is None:
+        return "nil"
+    if isinstance(v, bool):
+        return "true" if v else "false"
+    if isinstance(v, str):
+        return v if v.startswith(":") else '"' + v.replace("\\", "\\\\").replace('"', '\\"') + '"'
+    if isinstance(v, (list, tuple)):
+        return "[" + " ".join(pr_str(x) for x in v) + "]"
+    return str(v)
+
+
+_MOP_READ, _MOP_WRITE = ("r", "read", ":r"), ("w", "write", ":w")
+
+
+class MultiRegister:
+    """yugabyte.multi-key-acid/MultiRegister (multi_key_acid.clj:20-42, a copy of
+    knossos' multi-register): the state maps registers to values; an op's :value
+    is a txn [[f k v] ...] of reads and writes applied left to right; a read of
+    nil is always legal, any other read must see the register's value
+    (`(pr-str (get state k)) "≠" (pr-str v)` otherwise). A micro-op f other than
+    a read or a write has no clause (`case` throws). Searched on the device by
+    jh_check_multi_register (jepsen_amd/multi_register.py)."""
+
+    __slots__ = ("values",)
+
+    def __init__(self, values=None):
+        object.__setattr__(self, "values", dict(values or {}))
+
+    def __setattr__(self, k, v):
+        raise AttributeError("MultiRegister is immutable")
+
+    def __eq__(self, other):
+        return isinstance(other, MultiRegister) and self.values == other.values
+
+    def __hash__(self):
+        return hash(frozenset((k, repr(v)) for k, v in self.values.items()))
+
+    def __repr__(self):
+        return f"MultiRegister({self.values!r})"
+
+    def step(self, op):
+        state = self.values
+        copied = False
+        for mop in op.get("value") or ():
+            f, k, v = mop
+            if f in _MOP_READ:
+                if v is None or v == state.get(k):
+                    continue
+                return inconsistent(pr_str(state.get(k)) + "≠" + pr_str(v))
+            if f in _MOP_WRITE:
+                if not copied:
+                    state, copied = dict(state), True
+                state[k] = v
+                continue
+            raise ValueError(f"No matching clause: {f}")
+        return MultiRegister(state) if copied else self
+
+
+def multi_register(values=None):
+    """(multi-register values): values maps registers to their initial values."""
+    return MultiRegister(values)
+
+
 _MUTEX_CAS = {"acquire": [0, 1], "release": [1, 0]}
 
 

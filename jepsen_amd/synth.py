@@ -1353,3 +1353,86 @@ def perf_columns_to_ops(cols):
                     "f": known[c] if c in known else cols.f_names[c - A.F_FIRST_INTERNED], "time": int(cols.time[i]),
                     "index": i})
     return out
+
+
+# ---------------------------------------------------------------------------
+def multi_register_history(n_keys=64, ops_per_key=100, threads=10, regs=3, values=5, p_info=0.02, faulted_keys=(),
+                           seed=0, concurrent=4):
+    """Op maps of the multi-register workload (yugabyte multi_key_acid.clj:95-127),
+    keyed by independent tuples: per key `threads` threads invoke txns -- a
+    random non-empty subset of the `regs` registers, all reads ([:r k nil],
+    values filled in on the completion) or all writes of values below `values`
+    -- and a txn takes effect at a random point between its invocation and its
+    completion. With probability p_info an op crashes instead (an :info row; it
+    took effect or never will) and its thread goes on as process + threads
+    (core.clj:349). A faulted key has one micro-op of one :ok read changed to
+    another value; that does not always make the key invalid. faulted_keys: key
+    numbers, or how many (spread evenly). Keys run in groups of `concurrent`,
+    their rows interleaved."""
+    import random
+    from .history import tuple_
+    rng = random.Random(seed)
+    if isinstance(faulted_keys, int):
+        faulted_keys = [k * n_keys // faulted_keys for k in range(faulted_keys)] if faulted_keys > 0 else []
+    faulted = set(faulted_keys)
+
+    def one_key(k):
+        state, out, reads = {}, [], []
+        proc = list(range(threads))
+        pend = [None] * threads            # [f, txn, applied, result]
+        invoked = 0
+        while True:
+            live = [t for t in range(threads) if pend[t] is not None or invoked < ops_per_key]
+            if not live:
+                break
+            t = rng.choice(live)
+            p = pend[t]
+            if p is None:
+                sub = [r for r in range(regs) if rng.random() < 0.5] or [rng.randrange(regs)]
+                if rng.random() < 0.5:
+                    f, txn = "read", [["r", r, None] for r in sub]
+                else:
+                    f, txn = "write", [["w", r, rng.randrange(values)] for r in sub]
+                out.append({"process": proc[t], "type": "invoke", "f": f, "value": tuple_(k, txn)})
+                pend[t] = [f, txn, False, None]
+                invoked += 1
+                continue
+            crash = rng.random() < p_info
+            if not p[2] and not (crash and rng.random() < 0.5):
+                p[2] = True                # the txn takes effect
+                if p[0] == "read":
+                    p[3] = [["r", r, state.get(r)] for _, r, _ in p[1]]
+                else:
+                    for _, r, v in p[1]:
+                        state[r] = v
+                    p[3] = p[1]
+                if not crash:
+                    continue
+            if crash:
+                out.append({"process": proc[t], "type": "info", "f": p[0], "value": tuple_(k, p[1])})
+                proc[t] += threads
+            else:
+                if p[0] == "read":
+                    reads.append(len(out))
+                out.append({"process": proc[t], "type": "ok", "f": p[0], "value": tuple_(k, p[3])})
+            pend[t] = None
+        if k in faulted and reads:
+            op = out[rng.choice(reads)]
+            txn = [list(m) for m in op["value"].val]
+            m = rng.choice(txn)
+            m[2] = rng.choice([v for v in range(values) if v != m[2]] or [values])
+            op["value"] = tuple_(k, txn)
+        return out
+
+    history = []
+    for g in range(0, n_keys, max(1, concurrent)):
+        parts = [one_key(k) for k in range(g, min(n_keys, g + max(1, concurrent)))]
+        at = [0] * len(parts)
+        left = [i for i, p in enumerate(parts) if p]
+        while left:
+            i = rng.choice(left)
+            history.append(parts[i][at[i]])
+            at[i] += 1
+            if at[i] == len(parts[i]):
+                left.remove(i)
+    return history
